@@ -1,15 +1,20 @@
 """Benchmark: X2-GNN training step (molecules/s, fwd+bwd) on synthetic QM9-U0-shaped molecules.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 One step = the reference trainer's step (trainer.py:37-48) on one resident batch of 128
 molecules per GPU: xgnn_poly forward (GPU triplet build, basis, 4 SBF-transformer layers,
 readouts), smooth-L1 loss, backward, one RCCL all-reduce of the flat gradient bucket (N>1),
 grad-norm clip (max 100), Adam step and the EMA update.  Weak scaling: every rank owns its own
-128 molecules.  Rank 0 prints ONE JSON line (contract in the task statement); besides the
-metric it carries the dominant kernel's roofline (HIP-event timed here, on the stream it runs
-on) and the CPU baseline (the oracle restatement, torch-CPU, on a bounded sample).
+128 molecules.  Rank 0 prints ONE JSON line (contract in the task statement).
+
+A plain run sets up, captures and warms up the step, times ``--steps`` steps, writes the last
+step's outputs when ``--dump-outputs DIR`` is given, and prints the line with the metric.  With
+``--full`` the line also carries what takes runs of its own after the timed steps: the kernel
+probes and the dominant kernel's roofline (HIP-event timed here, on the stream it runs on), the
+step roofline, the scatter-add roofline, the per-batch host cost, the fresh-batch DataLoader rate
+and the CPU baseline (the oracle restatement, torch-CPU, on a bounded sample).
 """
 from __future__ import annotations
 
@@ -125,13 +130,18 @@ def parse():
                     help="molecules per step over all ranks (default: gpus x batch; BASELINE config 4 = 1024 "
                          "over 8); one global batch, sharded by triplet count (x2gnn.dist.shard_by_triplets)")
     ap.add_argument("--shape", default="S160", choices=["S160", "S5A"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-loader", action="store_true", help="skip the fresh-batch DataLoader side field")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements (kernel probes and rooflines, "
+                         "host batch cost, DataLoader rate, CPU baseline) and add them to the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-loader", action="store_true", help="--full without the fresh-batch DataLoader side field")
     ap.add_argument("--no-lazy-sbf", action="store_true", help="write the [T, 42] sbf rows (ops.LAZY_SBF False)")
     ap.add_argument("--device-schedule", action="store_true",
                     help="collate without the center schedule: the step makes it on the device (data.HOST_SCHEDULE)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--kernel-reps", type=int, default=20)
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the CPU baseline sample")
+    ap.add_argument("--kernel-reps", type=int, default=20, help="--full: launches per kernel probe")
     ap.add_argument("--eager", action="store_true", help="no HIP-graph capture of the step")
     ap.add_argument("--workload", default="qm9_u0", choices=sorted(WORKLOADS),
                     help="qm9_u0: BASELINE config 2 (the metric); qm9_allprop: config 3 (one target's model, "
@@ -725,104 +735,33 @@ def cpu_baseline(mols, budget_s, global_pool=None, train=True, sample=None):
                       f"same cores in the build container)"}
 
 
-# ------------------------------------------------------------------------------------------ main
-def main():
-    args = parse()
-    if args.no_lazy_sbf:
-        ops.LAZY_SBF = False
-    if args.device_schedule:
-        import x2gnn.data as xdata
+DUMP_BYTES = 64 * 2 ** 20  # all files of one --dump-outputs together
 
-        xdata.HOST_SCHEDULE = False
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    # one rank per GPU; ranks beyond the visible GPUs (a gloo rehearsal on a 1-GPU box) share them
-    local = local % max(1, torch.cuda.device_count())
-    if world > 1:
-        if args.dist_backend == "nccl":
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-        else:
-            dist.init_process_group("gloo")
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    torch.manual_seed(0)  # identical initial weights on every rank
 
-    wl = WORKLOADS[args.workload]
-    # one global batch of world * batch molecules (BASELINE config 4: 1024 = 8 x 128), the same on
-    # every rank, sharded by triplet count (x2gnn.dist.shard_by_triplets, SURVEY §8(e))
-    global_batch = args.global_batch if args.global_batch is not None else world * args.batch
-    if args.workload == "aid_infer":  # consecutive AID molecules (wrapping), real geometries
-        n_aid = int(np.load(AID_GEOM)["counts"].shape[0])
-        all_mols = molecules_from_geometry_file(AID_GEOM, indices=[i % n_aid for i in range(global_batch)], seed=0)
+def dump_outputs(path, runner, loss, train):
+    """--dump-outputs: what the last timed step handed its caller, as ``path``/<name>.npy in float32.
+    A training step returns the loss and leaves the updated parameters, their EMA (both as the flat
+    buffers of x2gnn.optim.FlatAdam, the model's parameters in order) and the gradient norm it
+    clipped by; an inference step returns the energies' sum.  Arrays that together would exceed
+    DUMP_BYTES are each cut to a fixed sample (sorted indices drawn once with seed 0)."""
+    if train:
+        out = {"loss": loss, "grad_norm": runner.opt.grad_norm, "params": runner.opt.flat, "ema": runner.opt.ema}
     else:
-        all_mols = synthetic_molecules(global_batch, args.shape, seed=1000)
-    shards = shard_by_triplets([m["triplet_num"] for m in all_mols], world)
-    mols = [all_mols[i] for i in shards[rank]]
-    # the shards' triplet totals: the straggler bound of the step (every rank waits for the largest)
-    shard_t = [int(sum(all_mols[i]["triplet_num"] for i in s)) for s in shards]
-    host_batch, n_local, _ = collate_shard(all_mols, world, rank)
-    batch = host_batch.to(dev)
-    # the per-batch host cost a data loader has to hide under the step (side fields, not `value`):
-    # collate (PyG Batch.from_data_list restated + the int32 index forms) and the H2D copy, warm; the median of
-    # 5 each (one sample read 5 to 15 ms for config 2's collate on the same box, host noise)
-    t_col, t_h2d = [], []
-    for _ in range(5):
-        t0 = time.perf_counter()
-        host_batch, _, _ = collate_shard(all_mols, world, rank)
-        t1 = time.perf_counter()
-        host_batch.to(dev)
-        torch.cuda.synchronize()
-        t_col.append(t1 - t0)
-        t_h2d.append(time.perf_counter() - t1)
-    t_c0, t_c1, t_c2 = 0.0, float(np.median(t_col)), float(np.median(t_col)) + float(np.median(t_h2d))
-    del host_batch, all_mols
-    global_pool = None
-    if args.workload == "qm9_allprop":
-        model = model_for_target(args.target, CFG, device="cuda").to(dev)  # train_ema.py:41-44
-        if args.target not in ATOMWISE_TARGETS:
-            global_pool = "mean"
-    else:
-        model = x2gnn.xgnn_poly(device="cuda", **CFG).to(dev)
-    runner = (Trainer(model, local_count=len(mols), global_count=global_batch) if wl["train"]
-              else Inference(model))
+        out = {"energy_sum": loss}
+    out = {k: v.detach().to(torch.float32).reshape(-1).cpu().numpy() for k, v in out.items() if v is not None}
+    total = sum(a.nbytes for a in out.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        keep = a.size if total <= DUMP_BYTES else max(1, int(a.size * (DUMP_BYTES / total)))
+        if keep < a.size:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
-    graphed = False
-    if not args.eager:
-        runner.capture(batch)  # its warm-up steps are extra, untimed
-        graphed = True
-    for _ in range(args.warmup):
-        runner.step(batch)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = runner.step(batch)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
-    t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-    if world > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    t_max = float(t.item())
-    final_loss = float(loss.item())
 
-    if args.step_only:
-        if rank == 0:
-            print(json.dumps({"value": round(global_batch * args.steps / t_max, 2),
-                              "ms_per_step": round(1e3 * t_max / args.steps, 4), "steps": args.steps,
-                              "final_loss": float(f"{final_loss:.6e}")}),
-                  flush=True)
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
-        return
-
-    meta = batch.host_meta()
+def kernel_fields(args, wl, model, runner, batch, sizes):
+    """--full: the kernel probes, the dominant kernel's roofline and the scatter-add roofline, each in
+    runs of its own after the timed steps; returns their fields of the line and sets ``sizes`` (E line
+    nodes, T triplets) to the planned line graph's."""
     traffic_path, traffic_table = load_traffic(args.workload, args.shape)
     probe, shape = attention_probe(model, batch, args.kernel_reps, train=wl["train"])
     plan_lg = model.line_graph_data(batch)[1].lg
@@ -872,6 +811,123 @@ def main():
                 "bytes_per_launch": int(a_bytes), "gathered_bytes_per_launch": int(a_gath),
                 "hbm_GBs": None if hbm is None else round(hbm / (a_ms * 1e-3) / 1e9, 1),
                 "traffic_source": os.path.relpath(traffic_path, ROOT) if hbm is not None else None}
+    sizes.update(E=shape["E"], T=shape["T"])  # (the planned line graph's own counts)
+    return {"roofline": roof,
+            "kernels": dict(
+                {k: _hbm_entry(k, v, traffic_table) for k, v in probe.items()},
+                **{k: _mfma_entry(k, v, traffic_table) for k, v in dense.items()}),
+            "roofline_scatter_add": {
+                "kernel": "x2g_segment_sum [T,128]->[E,128]", "bytes_per_launch": sa["bytes"],
+                "warm_GBs": round(sa["bytes"] / (sa["warm_ms"] * 1e-3) / 1e9, 1),
+                "cold_GBs": round(sa["bytes"] / (sa["cold_ms"] * 1e-3) / 1e9, 1),
+                "cold_frac": round(sa["bytes"] / (sa["cold_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                "parity": sa["parity"]}}
+
+
+# ------------------------------------------------------------------------------------------ main
+def main():
+    args = parse()
+    if args.no_lazy_sbf:
+        ops.LAZY_SBF = False
+    if args.device_schedule:
+        import x2gnn.data as xdata
+
+        xdata.HOST_SCHEDULE = False
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    # one rank per GPU; ranks beyond the visible GPUs (a gloo rehearsal on a 1-GPU box) share them
+    local = local % max(1, torch.cuda.device_count())
+    if world > 1:
+        if args.dist_backend == "nccl":
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+        else:
+            dist.init_process_group("gloo")
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    torch.manual_seed(0)  # identical initial weights on every rank
+
+    wl = WORKLOADS[args.workload]
+    # one global batch of world * batch molecules (BASELINE config 4: 1024 = 8 x 128), the same on
+    # every rank, sharded by triplet count (x2gnn.dist.shard_by_triplets, SURVEY §8(e))
+    global_batch = args.global_batch if args.global_batch is not None else world * args.batch
+    if args.workload == "aid_infer":  # consecutive AID molecules (wrapping), real geometries
+        n_aid = int(np.load(AID_GEOM)["counts"].shape[0])
+        all_mols = molecules_from_geometry_file(AID_GEOM, indices=[i % n_aid for i in range(global_batch)], seed=0)
+    else:
+        all_mols = synthetic_molecules(global_batch, args.shape, seed=1000)
+    shards = shard_by_triplets([m["triplet_num"] for m in all_mols], world)
+    mols = [all_mols[i] for i in shards[rank]]
+    # the shards' triplet totals: the straggler bound of the step (every rank waits for the largest)
+    shard_t = [int(sum(all_mols[i]["triplet_num"] for i in s)) for s in shards]
+    host_batch, n_local, _ = collate_shard(all_mols, world, rank)
+    batch = host_batch.to(dev)
+    # the per-batch host cost a data loader has to hide under the step (side fields, not `value`):
+    # collate (PyG Batch.from_data_list restated + the int32 index forms) and the H2D copy, warm; the median of
+    # 5 each (one sample read 5 to 15 ms for config 2's collate on the same box, host noise)
+    t_col, t_h2d = [], []
+    for _ in range(5 if args.full else 0):  # (a plain run does not measure it)
+        t0 = time.perf_counter()
+        host_batch, _, _ = collate_shard(all_mols, world, rank)
+        t1 = time.perf_counter()
+        host_batch.to(dev)
+        torch.cuda.synchronize()
+        t_col.append(t1 - t0)
+        t_h2d.append(time.perf_counter() - t1)
+    if args.full:
+        t_c0, t_c1, t_c2 = 0.0, float(np.median(t_col)), float(np.median(t_col)) + float(np.median(t_h2d))
+    del host_batch, all_mols
+    global_pool = None
+    if args.workload == "qm9_allprop":
+        model = model_for_target(args.target, CFG, device="cuda").to(dev)  # train_ema.py:41-44
+        if args.target not in ATOMWISE_TARGETS:
+            global_pool = "mean"
+    else:
+        model = x2gnn.xgnn_poly(device="cuda", **CFG).to(dev)
+    runner = (Trainer(model, local_count=len(mols), global_count=global_batch) if wl["train"]
+              else Inference(model))
+
+    graphed = False
+    if not args.eager:
+        runner.capture(batch)  # its warm-up steps are extra, untimed
+        graphed = True
+    for _ in range(args.warmup):
+        runner.step(batch)
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        loss = runner.step(batch)
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+    if world > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    t_max = float(t.item())
+    final_loss = float(loss.item())
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, runner, loss, wl["train"])
+
+    if args.step_only:
+        if rank == 0:
+            print(json.dumps({"value": round(global_batch * args.steps / t_max, 2),
+                              "ms_per_step": round(1e3 * t_max / args.steps, 4), "steps": args.steps,
+                              "final_loss": float(f"{final_loss:.6e}")}),
+                  flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    meta = batch.host_meta()
+    # line nodes (= directed edges) and triplets of this rank's batch
+    sizes = {"E": int(meta["edges"].sum()), "T": int(meta["triplets"].sum())}
+    side = kernel_fields(args, wl, model, runner, batch, sizes) if args.full else {}
     if args.workload == "aid_infer":
         data_desc = (f"AID_kcal geometries (tests/golden/aid_geom.npz = the reference's raw/AID_kcal.xyz; "
                      f"{meta['nodes'].mean():.1f} atoms, {meta['edges'].mean():.0f} directed edges, "
@@ -908,32 +964,27 @@ def main():
                        "shard_triplets": shard_t if world > 1 else None,
                        "imbalance_max_over_mean": (round(max(shard_t) / (sum(shard_t) / world), 5)
                                                    if world > 1 else None),
-                       "line_nodes_per_gpu": shape["E"], "triplets_per_gpu": shape["T"],
+                       "line_nodes_per_gpu": sizes["E"], "triplets_per_gpu": sizes["T"],
                        "parallelism": f"dp{world}", "hip_graph": graphed,
                        "grad_allreduce": None if world == 1 else (
                            "RCCL" if args.dist_backend == "nccl" else "gloo (rehearsal)")},
-            "roofline": roof,
-            "step_roofline": step_roofline(round(1e3 * t_max / args.steps, 4), args.workload, args.shape),
-            "kernels": dict(
-                {k: _hbm_entry(k, v, traffic_table) for k, v in probe.items()},
-                **{k: _mfma_entry(k, v, traffic_table) for k, v in dense.items()}),
-            "roofline_scatter_add": {
-                "kernel": "x2g_segment_sum [T,128]->[E,128]", "bytes_per_launch": sa["bytes"],
-                "warm_GBs": round(sa["bytes"] / (sa["warm_ms"] * 1e-3) / 1e9, 1),
-                "cold_GBs": round(sa["bytes"] / (sa["cold_ms"] * 1e-3) / 1e9, 1),
-                "cold_frac": round(sa["bytes"] / (sa["cold_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                "parity": sa["parity"]},
             ("final_loss" if wl["train"] else "energy_sum"): float(f"{final_loss:.6e}"),  # (one resident batch: memorised)
+        }
+        if args.full:
+            line["roofline"] = side["roofline"]
+            line["step_roofline"] = step_roofline(line["ms_per_step"], args.workload, args.shape)
+            line["kernels"] = side["kernels"]
+            line["roofline_scatter_add"] = side["roofline_scatter_add"]
             # per-batch host cost a loader must hide under the step (not in `value`: inputs are
             # resident in HBM when the timed region starts)
-            "host_batch_ms": {"collate": round(1e3 * (t_c1 - t_c0), 3), "h2d": round(1e3 * (t_c2 - t_c1), 3),
-                              "molecules": len(mols)},
-        }
-        if wl["train"] and world == 1 and args.workload == "qm9_u0" and not args.no_loader:
-            line["loader"] = loader_probe(CFG, dev, shape=args.shape)
-        if not args.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = cpu_baseline(mols, args.cpu_seconds, global_pool=global_pool, train=wl["train"],
-                                                sample=8 if args.workload == "aid_infer" else None)
+            line["host_batch_ms"] = {"collate": round(1e3 * (t_c1 - t_c0), 3), "h2d": round(1e3 * (t_c2 - t_c1), 3),
+                                     "molecules": len(mols)}
+            if wl["train"] and world == 1 and args.workload == "qm9_u0" and not args.no_loader:
+                line["loader"] = loader_probe(CFG, dev, shape=args.shape)
+            if not args.no_cpu_baseline and world == 1:
+                line["cpu_baseline"] = cpu_baseline(mols, args.cpu_seconds, global_pool=global_pool,
+                                                    train=wl["train"],
+                                                    sample=8 if args.workload == "aid_infer" else None)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

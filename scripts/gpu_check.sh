@@ -24,23 +24,23 @@ for s in "$@"; do
     ab) step ab 900 python -u scripts/step_ab.py ${AB_ROUNDS:-3} $AB_VARIANTS ;;
     gpu) step gputests 900 python -u -m pytest tests -q -m gpu -rf --timeout 600 --timeout-method thread ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 420 python bench.py ;;
+    bench) step bench 420 python bench.py --full ;;
     dist2) step dist2 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-            --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 3 --dist-backend gloo --no-cpu-baseline ;;
-    bench_c3) step bench_c3 420 python bench.py --workload qm9_allprop --target 0 ;;
-    bench_c3a) step bench_c3a 420 python bench.py --workload qm9_allprop --target 7 --no-cpu-baseline ;;
-    bench_c5) step bench_c5 420 python bench.py --workload aid_infer --steps 50 --warmup 5 ;;
+            --master-port 29517 bench.py --full --gpus 2 --steps 10 --warmup 3 --dist-backend gloo --no-cpu-baseline ;;
+    bench_c3) step bench_c3 420 python bench.py --full --workload qm9_allprop --target 0 ;;
+    bench_c3a) step bench_c3a 420 python bench.py --full --workload qm9_allprop --target 7 --no-cpu-baseline ;;
+    bench_c5) step bench_c5 420 python bench.py --full --workload aid_infer --steps 50 --warmup 5 ;;
     prof_c5) step prof_c5 420 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c5_$TAG -o run --output-format csv \
-            -- python "$ROOT/bench.py" --workload aid_infer --steps 5 --warmup 2 --no-cpu-baseline ;;
+            -- python "$ROOT/bench.py" --full --workload aid_infer --steps 5 --warmup 2 --no-cpu-baseline ;;
     prof) step prof 420 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run --output-format csv \
-            -- python "$ROOT/bench.py" --steps 20 --warmup 3 --no-cpu-baseline ;;
+            -- python "$ROOT/bench.py" --full --steps 20 --warmup 3 --no-cpu-baseline ;;
     pmc) step pmc 420 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d gpurun_out/pmc_fetch_$TAG -o run \
-            --output-format csv -- python "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3 &&
+            --output-format csv -- python "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3 &&
          step pmc2 420 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d gpurun_out/pmc_write_$TAG -o run \
-            --output-format csv -- python "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3 ;;
+            --output-format csv -- python "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3 ;;
     pmc_c5) step pmc_c5 420 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d gpurun_out/pmc_fetch_c5_$TAG -o run \
-            --output-format csv -- python "$ROOT/bench.py" --workload aid_infer --steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3 &&
+            --output-format csv -- python "$ROOT/bench.py" --full --workload aid_infer --steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3 &&
          step pmc_c5w 420 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d gpurun_out/pmc_write_c5_$TAG -o run \
-            --output-format csv -- python "$ROOT/bench.py" --workload aid_infer --steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3 ;;
+            --output-format csv -- python "$ROOT/bench.py" --full --workload aid_infer --steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3 ;;
   esac
 done

@@ -25,7 +25,7 @@ pmc2() {  # pmc2 <name> <bench args...>: FETCH_SIZE pass, WRITE_SIZE pass, summa
 # bench (the four bench lines), prof (config 2's bench command under rocprofv3 --kernel-trace --stats)
 PARTS=${PARTS:-pmc work bench}
 has() { [[ " $PARTS " == *" $1 "* ]]; }
-P="--steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3"
+P="--full --steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3"
 if has pmc; then
 pmc2 c2 $P
 pmc2 s5a $P --shape S5A
@@ -46,11 +46,11 @@ cp gpurun_out/step_work_$TAG.json profiles/r4_step_work.json
 fi
 # the bench lines read the summaries installed above (on this box; the caller copies them into profiles/)
 has bench || exit 0
-run bench_c2 420 python bench.py
+run bench_c2 420 python bench.py --full
 # the same command under rocprofv3 (kernel stats: the roofline kernel's average launch must agree)
 if has prof; then
 run prof_c2 420 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c2_$TAG -o run --output-format csv -- python "$ROOT/bench.py" --no-cpu-baseline
 fi
-run bench_s5a 420 python bench.py --shape S5A --no-cpu-baseline
-run bench_c3 420 python bench.py --workload qm9_allprop --target 0
-run bench_c5 420 python bench.py --workload aid_infer --steps 50 --warmup 5
+run bench_s5a 420 python bench.py --full --shape S5A --no-cpu-baseline
+run bench_c3 420 python bench.py --full --workload qm9_allprop --target 0
+run bench_c5 420 python bench.py --full --workload aid_infer --steps 50 --warmup 5

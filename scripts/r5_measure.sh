@@ -31,7 +31,7 @@ has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has tests; then
 run gputests 1000 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 fi
-P="--steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3"
+P="--full --steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 3"
 if has pmc; then
 pmc2 c2 $P
 pmc2 s5a $P --shape S5A
@@ -52,11 +52,11 @@ cp gpurun_out/step_work_$TAG.json profiles/${R}_step_work.json
 fi
 # the bench lines read the summaries installed above (on this box; the caller copies them into profiles/)
 has bench || exit 0
-run bench_c2 420 python bench.py
+run bench_c2 420 python bench.py --full
 # the same command under rocprofv3 (kernel stats: the roofline kernel's average launch must agree)
 if has prof; then
 run prof_c2 420 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c2_$TAG -o run --output-format csv -- python "$ROOT/bench.py" --no-cpu-baseline
 fi
-run bench_s5a 420 python bench.py --shape S5A --no-cpu-baseline
-run bench_c3 420 python bench.py --workload qm9_allprop --target 0
-run bench_c5 420 python bench.py --workload aid_infer --steps 50 --warmup 5
+run bench_s5a 420 python bench.py --full --shape S5A --no-cpu-baseline
+run bench_c3 420 python bench.py --full --workload qm9_allprop --target 0
+run bench_c5 420 python bench.py --full --workload aid_infer --steps 50 --warmup 5

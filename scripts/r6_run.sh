@@ -29,16 +29,16 @@ for s in "$@"; do
     dist) step dist 600 $PT tests/test_dist_gpu.py tests/test_rccl_gpu.py ;;
     gpu) step gputests 1000 $PT tests ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    c2) step bench_c2 300 python bench.py --no-cpu-baseline ;;
-    c2full) step bench_c2full 420 python bench.py ;;
-    c2dev) step bench_c2dev 300 python bench.py --no-cpu-baseline --device-schedule ;;
-    s5a) step bench_s5a 300 python bench.py --shape S5A --no-cpu-baseline ;;
-    c3) step bench_c3 300 python bench.py --workload qm9_allprop --target 0 --no-cpu-baseline ;;
-    c5) step bench_c5 300 python bench.py --workload aid_infer --steps 50 --warmup 5 --no-cpu-baseline ;;
+    c2) step bench_c2 300 python bench.py --full --no-cpu-baseline ;;
+    c2full) step bench_c2full 420 python bench.py --full ;;
+    c2dev) step bench_c2dev 300 python bench.py --full --no-cpu-baseline --device-schedule ;;
+    s5a) step bench_s5a 300 python bench.py --full --shape S5A --no-cpu-baseline ;;
+    c3) step bench_c3 300 python bench.py --full --workload qm9_allprop --target 0 --no-cpu-baseline ;;
+    c5) step bench_c5 300 python bench.py --full --workload aid_infer --steps 50 --warmup 5 --no-cpu-baseline ;;
     prof_c2) step prof_c2 420 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c2_$TAG -o run --output-format csv \
-            -- python "$ROOT/bench.py" --steps 50 --warmup 3 --no-cpu-baseline ;;
+            -- python "$ROOT/bench.py" --full --steps 50 --warmup 3 --no-cpu-baseline ;;
     prof_c5) step prof_c5 420 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c5_$TAG -o run --output-format csv \
-            -- python "$ROOT/bench.py" --workload aid_infer --steps 10 --warmup 2 --no-cpu-baseline ;;
+            -- python "$ROOT/bench.py" --full --workload aid_infer --steps 10 --warmup 2 --no-cpu-baseline ;;
     ab) step ab 900 python -u scripts/step_ab.py ${AB_ROUNDS:-3} $AB_VARIANTS ;;
     ab_c5) step ab_c5 900 python -u scripts/step_ab.py ${AB_ROUNDS:-3} $AB_VARIANTS ;;
     *) echo "unknown step $s"; exit 2 ;;

@@ -47,7 +47,7 @@ def test_read_xyz_keeps_reference_quirks(tmp_path):
     assert len(ds.read_xyz(_write(tmp_path, "c.xyz", XYZ_TWO + "\n"))) == 1
 
 
-REF_AID = "/root/reference/raw/AID_kcal.xyz"
+AID_XYZ = os.path.join(GOLDEN, "AID_kcal.xyz.xz")  # the reference's raw/AID_kcal.xyz, xz-compressed
 
 
 def _check_against_reference(recs, z, prefix):
@@ -79,12 +79,17 @@ def test_read_xyz_quirks_equal_reference(tmp_path):
         _check_against_reference(recs, z, name + "_")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_AID), reason="the reference's raw/AID_kcal.xyz is only in the build container")
-def test_read_xyz_aid_equals_reference():
-    """The whole AID_kcal.xyz (config 5's data) parsed here == the reference's own parse, and the
-    committed aid_geom.npz (what the GPU box rebuilds config 5 from) is that parse."""
+def test_read_xyz_aid_equals_reference(tmp_path):
+    """The whole AID_kcal.xyz (config 5's data, stored compressed beside the fixtures) parsed here ==
+    the reference's own parse, and the committed aid_geom.npz (what config 5 is rebuilt from) is that
+    parse."""
+    import lzma
+
     z = golden("xyz_ref.npz")
-    _check_against_reference(ds.read_xyz(REF_AID), z, "aid_")
+    path = tmp_path / "AID_kcal.xyz"
+    with lzma.open(AID_XYZ, "rb") as f:
+        path.write_bytes(f.read())
+    _check_against_reference(ds.read_xyz(str(path)), z, "aid_")
 
 
 def test_aid_geometry_fixture_is_reference_parse():
