@@ -793,6 +793,12 @@ int x2g_clip_adam_ema_ex(float* params, float* grads, float* exp_avg, float* exp
                                 not span it, and a stage adds one residual at most) */
 #define X2G_CHAIN_RES_ACCUM 16 /* backward only, with RES_EXT: d_res_ext += (instead of =) the
                                   residual's gradient (res_ext feeds other layers too) */
+#define X2G_CHAIN_IN0_ROWMAJOR 32 /* forward only, stage 0 only (X2G_EINVAL on another stage): plane 0 of
+                                     in_t (the chain's input) is not written, because the caller keeps that
+                                     input row-major (x, or x_norm of x2g_chain_fwd_ln) and hands it to the
+                                     stage-0 weight gradient as an X2G_TILED_X_ROWMAJOR operand; planes
+                                     1..n-1 keep their offsets.  Not for x2g_chain_wgrad, which reads
+                                     contiguous T planes. */
 
 typedef struct {
   const float* w; /* [D, D] nn.Linear weight, row n = output feature n */
@@ -919,7 +925,8 @@ int x2g_conv_proj_fwd(const float* x, const float* rbf, int32_t rbf_dim, const f
 
 /* The gradients x2g_conv_proj_fwd's backward takes: grads[0..3] = dL/d(q, k, v, skip) with their
  * weights (w, or wt when given) and optional T-layout copies g_t for the weight gradient
- * (x2g_tiled_wgrad):  dx = dq Wq + dskip Ws (+ dx_add; dx may alias dx_add),  dxs = dk Wk + dv Wv
+ * (x2g_tiled_wgrad; all four NULL: the kernel instance without any copy code, for a weight gradient that
+ * reads g itself, X2G_TILED_DY_ROWMAJOR):  dx = dq Wq + dskip Ws (+ dx_add; dx may alias dx_add),  dxs = dk Wk + dv Wv
  * = dL/d x_src. */
 typedef struct {
   const float* g;
@@ -950,7 +957,16 @@ typedef struct {
   float* db;
   int32_t ld;   /* 0: dw is a [D, D] weight; > 0: dw is the top-left of a D x D block of a larger */
   int32_t cols; /* weight with row stride ld, of which the first `cols` (<= D) columns are written */
+  /* Operand layouts (x2g_tiled_wgrad_flat / _flat_rows; x2g_tiled_wgrad takes 0 only).  0: both in the T
+   * layout.  X2G_TILED_DY_ROWMAJOR: dy_t points at a row-major [rows, D] tensor; X2G_TILED_X_ROWMAJOR:
+   * x_t does.  A row-major operand gives the same bits as its T-layout copy (rows past `rows` in the
+   * last tile count as zero, as the T layout's padding does).  Appended after `cols`, so callers that
+   * fill the first four or six fields keep today's meaning: x2g_abi_version() stays 17. */
+  int32_t layout;
+  int32_t pad_;
 } x2g_tiled_job;
+#define X2G_TILED_DY_ROWMAJOR 1
+#define X2G_TILED_X_ROWMAJOR 2
 
 /* The same for up to X2G_TILED_MAX_JOBS jobs (e.g. every T-layout weight gradient of a backward)
  * in ONE launch: the jobs' 16-row tiles are concatenated and split evenly over one workgroup per

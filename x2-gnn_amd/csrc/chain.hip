@@ -687,7 +687,8 @@ __device__ __forceinline__ void chain_fwd_v4_run(const ChainFwdArgs& a, const Ch
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) held[rb] = zero4();
     __syncthreads();
-    if (a.in_t) {
+    // (IN0_ROWMAJOR: the weight gradient reads the chain's input row-major, no T plane 0)
+    if (a.in_t && !(a.st[0].flags & X2G_CHAIN_IN0_ROWMAJOR)) {
       f4 xs[RB];
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb) xs[rb] = img0[ipos(16 * rb + rl, 4 * w + g)];
@@ -1125,36 +1126,67 @@ __device__ __forceinline__ void tiled_segment(const float* __restrict__ dz, cons
 // (vmcnt(0)) before the step's first LDS read: step i + 1's copy never ran under step i's MFMAs.  The
 // next step's copy is issued unconditionally (past the segment's end it re-reads tile t0 into the idle
 // buffer, drained at the end), since a branch around it would merge two wait histories into vmcnt(0).
-template <bool SPREAD, int WT>
+// Row-major operands (DR: dz, XR: xin point at [rows, 128] tensors, not T tiles).  A 16-row tile of a
+// row-major tensor is 8 KB contiguous as well; its image keeps rows whole and swizzles the 16-byte
+// chunks: chunk (r, c) at position 32 r + (c ^ (r & 12)), i.e. float (r, f) at rpos(r, f).  The lane
+// (rl, g) then reads feature f's rows 4g .. 4g+3 as four ds_read_b32, 128 floats apart (the bank is
+// 16 ((f >> 4 & 3) ^ g) + f % 16: a bijection of (g, rl), conflict-free), into the same av[e] / bv[bk][e]
+// a T image's ds_read_b128 gives: the MFMA K mapping (slot g of MFMA e = row 4g + e), the accumulation
+// order and the bias sums are the T path's, so a row-major operand gives the bits of its T copy.
+// Rows past `rows` (the last tile's tail, which the T layout pads with zeros) are past the buffer
+// descriptor's range and land as zeros.
+__device__ __forceinline__ int rpos(int r, int f) { return 128 * r + 4 * ((f >> 2) ^ (r & 12)) + (f & 3); }
+
+template <bool SPREAD, int WT, bool DR, bool XR>
 __device__ __forceinline__ void tiled_segment2(const float* __restrict__ dz, const float* __restrict__ xin, int64_t t0,
-                                               int64_t t1, bool has_b, float* __restrict__ slab,
+                                               int64_t t1, int64_t rows, bool has_b, float* __restrict__ slab,
                                                float* __restrict__ slab_b, f4 (*D0)[512], f4 (*X0)[512],
-                                               f4 (*D1)[512], f4 (*X1)[512]) {
+                                               f4 (*D1)[512], f4 (*X1)[512], float* __restrict__ bred) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int rl = lane & 15, g = lane >> 4;
   const int nsteps = static_cast<int>((t1 - t0 + WT - 1) / WT);
   const int P = 64 * w + lane;
-  const int src_chunk = (P >> 2) * 4 + ((P & 3) ^ (((P >> 5) & 1) * 3));
+  // LDS position P of a tile image holds this source chunk of the tile
+  const int chunk_t = (P >> 2) * 4 + ((P & 3) ^ (((P >> 5) & 1) * 3));
+  const int chunk_r = (P & ~31) | ((P & 31) ^ ((P >> 5) & 12));
+  const int d_chunk = DR ? chunk_r : chunk_t, x_chunk = XR ? chunk_r : chunk_t;
   // buffer_load ... lds over the segment's tiles (global_load_lds carried no LDS memory operand the
   // compiler could tell apart, so it waited on it before any LDS read even with separate buffers)
   const int64_t nt = t1 - t0;
   const int nbytes = static_cast<int>(nt * 8192 < 0x7fffffff ? nt * 8192 : 0x7fffffff);
-  const rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dz + t0 * 2048), static_cast<short>(0), nbytes,
-                                                      0x00020000);
-  const rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xin + t0 * 2048), static_cast<short>(0), nbytes,
-                                                      0x00020000);
+  // a row-major operand ends at its last row: the chunks of a partial last tile past it read as zero
+  const int64_t rend = t1 * 16 < rows ? t1 * 16 : rows;
+  // (fits an int because flat_tiles() admits only jobs of rows * 512 < 2^31 bytes; clamped like nbytes all the same)
+  const int64_t rb64 = (rend - t0 * 16) * (kCD * 4);
+  const int rbytes = static_cast<int>(rb64 < 0x7fffffff ? rb64 : 0x7fffffff);
+  const rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dz + t0 * 2048), static_cast<short>(0),
+                                                      DR ? rbytes : nbytes, 0x00020000);
+  const rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xin + t0 * 2048), static_cast<short>(0),
+                                                      XR ? rbytes : nbytes, 0x00020000);
   auto issue = [&](int step, f4 (*Dd)[512], f4 (*Xd)[512]) {  // tiles past t1: tile t0
 #pragma unroll
     for (int k = 0; k < WT; ++k) {
       int tt = step * WT + k;
       tt = tt < nt ? tt : 0;
-      const int vo = tt * 8192 + 16 * src_chunk;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(dr, (__attribute__((address_space(3))) void*)(&Dd[k][64 * w]), 16, vo, 0,
-                                               0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (__attribute__((address_space(3))) void*)(&Xd[k][64 * w]), 16, vo, 0,
-                                               0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(dr, (__attribute__((address_space(3))) void*)(&Dd[k][64 * w]), 16,
+                                               tt * 8192 + 16 * d_chunk, 0, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (__attribute__((address_space(3))) void*)(&Xd[k][64 * w]), 16,
+                                               tt * 8192 + 16 * x_chunk, 0, 0, 0);
     }
   };
+  // rows 4q .. 4q+3 of feature f from a tile image, in either layout
+  auto quad = [&](const f4* im, bool rowmajor, int f, int q) {
+    if (!rowmajor) return im[tpos(f, q)];
+    const float* fm = reinterpret_cast<const float*>(im) + rpos(4 * q, f);
+    f4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = fm[128 * e];
+    return v;
+  };
+  // the row-major X image: feature 16 bk + rl's rows 4g .. at xb[bk & 3] + 64 (bk >> 2) (+ 128 e)
+  int xb[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) xb[j] = rpos(4 * g, 16 * j + rl);
   f4 acc[8];
 #pragma unroll
   for (int bk = 0; bk < 8; ++bk) acc[bk] = zero4();
@@ -1167,22 +1199,30 @@ __device__ __forceinline__ void tiled_segment2(const float* __restrict__ dz, con
 #pragma unroll
     for (int k = 0; k < WT; ++k) {
       if (t0 + static_cast<int64_t>(i) * WT + k >= t1) break;  // wave-uniform
-      const f4 av = Dc[k][tpos(16 * w + rl, g)];
+      const f4 av = quad(Dc[k], DR, 16 * w + rl, g);
       f4 bv[8];
+      if (XR) {
+        const float* fm = reinterpret_cast<const float*>(Xc[k]);
 #pragma unroll
-      for (int bk = 0; bk < 8; ++bk) bv[bk] = Xc[k][tpos(16 * bk + rl, g)];
+        for (int bk = 0; bk < 8; ++bk)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) bv[bk][e] = fm[xb[bk & 3] + 64 * (bk >> 2) + 128 * e];
+      } else {
+#pragma unroll
+        for (int bk = 0; bk < 8; ++bk) bv[bk] = Xc[k][tpos(16 * bk + rl, g)];
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e)
 #pragma unroll
         for (int bk = 0; bk < 8; ++bk) acc[bk] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[bk][e], acc[bk], 0, 0, 0);
       if (SPREAD && has_b) {
-        const f4 v = Dc[k][tpos(tid & (kCD - 1), tid >> 7)];
+        const f4 v = quad(Dc[k], DR, tid & (kCD - 1), tid >> 7);
         bsum += (v[0] + v[1]) + (v[2] + v[3]);
       }
       if (!SPREAD && tid < 128) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const f4 v = Dc[k][tpos(tid, q)];
+          const f4 v = quad(Dc[k], DR, tid, q);
           bsum += (v[0] + v[1]) + (v[2] + v[3]);
         }
       }
@@ -1201,7 +1241,6 @@ __device__ __forceinline__ void tiled_segment2(const float* __restrict__ dz, con
     for (int e = 0; e < 4; ++e) slab[(16 * w + 4 * g + e) * kCD + 16 * bk + rl] = acc[bk][e];
   if (!SPREAD && has_b && tid < 128) slab_b[tid] = bsum;
   if (SPREAD && has_b) {  // the four row-quad partials of each feature, in quad order
-    __shared__ float bred[4 * kCD];
     bred[tid] = bsum;
     __syncthreads();
     if (tid < kCD) slab_b[tid] = ((bred[tid] + bred[kCD + tid]) + bred[2 * kCD + tid]) + bred[3 * kCD + tid];
@@ -1230,6 +1269,8 @@ struct TiledFlatArgs {
   float* slab_b[X2G_TILED_MAX_JOBS];  // ... and its bias slab at + k * D
   int wg_lo[X2G_TILED_MAX_JOBS];
   int has_b[X2G_TILED_MAX_JOBS];
+  int layout[X2G_TILED_MAX_JOBS];  // X2G_TILED_DY_ROWMAJOR | X2G_TILED_X_ROWMAJOR
+  int rows[X2G_TILED_MAX_JOBS];    // the job's rows (where a row-major operand ends)
   int64_t tile0[X2G_TILED_MAX_JOBS + 1];  // job j: tiles [tile0[j], tile0[j + 1]) of the concatenation
   int64_t total;
   int njobs;
@@ -1243,6 +1284,7 @@ __global__ void __launch_bounds__(kCThreads, 2 * WPC) tiled_flat_kernel(const Ti
   __shared__ f4 X0[WT][512];
   __shared__ f4 D1[WT][512];
   __shared__ f4 X1[WT][512];
+  __shared__ float bred[4 * kCD];  // the bias row-quad partials
   const int64_t G = gridDim.x, i = blockIdx.x;
   const int64_t lo = i * a.total / G, hi = (i + 1) * a.total / G;
   int j0 = 0;
@@ -1253,8 +1295,20 @@ __global__ void __launch_bounds__(kCThreads, 2 * WPC) tiled_flat_kernel(const Ti
     if (s0 >= s1) continue;
     __syncthreads();  // a previous segment's last buffers are no longer read
     const int64_t k = i - a.wg_lo[j];
-    tiled_segment2<SPREAD, WT>(a.dz_t[j], a.in_t[j], s0 - a.tile0[j], s1 - a.tile0[j], a.has_b[j] != 0,
-                               a.slab_w[j] + k * kCD * kCD, a.slab_b[j] + k * kCD, D0, X0, D1, X1);
+    // one instance of the step loop per operand layout pair (workgroup-uniform; T / T is the one before)
+    auto seg = [&](auto dr, auto xr) {
+      tiled_segment2<SPREAD, WT, decltype(dr)::value, decltype(xr)::value>(
+          a.dz_t[j], a.in_t[j], s0 - a.tile0[j], s1 - a.tile0[j], a.rows[j], a.has_b[j] != 0,
+          a.slab_w[j] + k * kCD * kCD, a.slab_b[j] + k * kCD, D0, X0, D1, X1, bred);
+    };
+    using T_ = std::false_type;
+    using R_ = std::true_type;
+    switch (a.layout[j]) {
+      case 0: seg(T_{}, T_{}); break;
+      case X2G_TILED_DY_ROWMAJOR: seg(R_{}, T_{}); break;
+      case X2G_TILED_X_ROWMAJOR: seg(T_{}, R_{}); break;
+      default: seg(R_{}, R_{}); break;
+    }
   }
 }
 
@@ -1418,7 +1472,8 @@ struct ProjBwdGateArgs {
 };
 
 
-template <int NJ, bool TW>  // TW: every projection's W^T given (else W read transposed)
+template <int NJ, bool TW, bool TC>  // TW: every projection's W^T given (else W read transposed); TC: T-layout
+// copies of the four gradients wanted (g_t; else no copy code at all: the weight gradient reads g row-major)
 __global__ void __launch_bounds__(kCThreads, 2) conv_proj_bwd_gate_kernel(const ProjBwdGateArgs a) {
   constexpr int RB = kGateRB;
   constexpr int kImg = RB * 16 * 32;
@@ -1448,6 +1503,7 @@ __global__ void __launch_bounds__(kCThreads, 2) conv_proj_bwd_gate_kernel(const 
       load_slice<true>(a.gr[p].w, w, rl, g, dst);
   };
   auto t_copy = [&](int p, const f4* im, int r0, int nrows) {  // the weight gradient's dy operand
+    if (!TC) return;
     f4 v[RB];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) v[rb] = im[ipos(16 * rb + rl, 4 * w + g)];
@@ -1466,10 +1522,11 @@ __global__ void __launch_bounds__(kCThreads, 2) conv_proj_bwd_gate_kernel(const 
   const rsrc_t bo = rsrc_n(a.drbf, a.R * a.RR * 4, a.drbf != nullptr && a.drbf_acc);
   static_assert(RB * 16 * NJ <= kCThreads && RB * 16 * kRbfMax <= kCThreads, "one srbf / drbf element per thread");
   // outstanding operations a pair's top wait may leave (issued after the pair's copies): 2 RB
-  // T-layout stores, the next weight slices (kWL loads each) and, at a (dk, dv) top, RB dx stores
+  // T-layout stores (TC only), the next weight slices (kWL loads each) and, at a (dk, dv) top, RB dx stores
   constexpr int kWL = TW ? 8 : 32;
-  constexpr int kKVWait = 3 * RB + 2 * kWL < 63 ? 3 * RB + 2 * kWL : 63;
-  constexpr int kQSWait = 2 * RB + 2 * kWL < 63 ? 2 * RB + 2 * kWL : 63;
+  constexpr int kTS = TC ? 2 * RB : 0;
+  constexpr int kKVWait = kTS + RB + 2 * kWL < 63 ? kTS + RB + 2 * kWL : 63;
+  constexpr int kQSWait = kTS + 2 * kWL < 63 ? kTS + 2 * kWL : 63;
   if (nk > 0) {
     int r0, nrows;
     chunk(0, r0, nrows);
@@ -1513,6 +1570,9 @@ __global__ void __launch_bounds__(kCThreads, 2) conv_proj_bwd_gate_kernel(const 
       const int r = tid / NJ, j = tid % NJ;
       rbv = bload1(rr, (tid < RB * 16 * NJ && r < nrows && j < a.RR) ? 4 * ((r0 + r) * a.RR + j) : kOOB, 0);
     }
+    // (without the T-layout stores nothing else keeps this load up here: sunk to its use below, after the
+    // weight slices, its wait would be vmcnt(0))
+    if (!TC) asm volatile("" ::: "memory");
     t_copy(1, img_k, r0, nrows);
     t_copy(2, img_v, r0, nrows);
     f4 acc1[RB];
@@ -1629,7 +1689,9 @@ static int chain_fwd_prepare(const float* x, const float* res_ext, const x2g_cha
   for (int s = 0; s < n_stages; ++s) {
     const x2g_chain_stage& S = stages[s];
     if (!S.w || (s == n_stages - 1 && !S.y)) return X2G_EINVAL;
-    if (S.flags & ~(X2G_CHAIN_SILU | X2G_CHAIN_HOLD | X2G_CHAIN_RES_HELD | X2G_CHAIN_RES_EXT)) return X2G_EINVAL;
+    if (S.flags & ~(X2G_CHAIN_SILU | X2G_CHAIN_HOLD | X2G_CHAIN_RES_HELD | X2G_CHAIN_RES_EXT |
+                    (s == 0 ? X2G_CHAIN_IN0_ROWMAJOR : 0)))
+      return X2G_EINVAL;
     // one register set holds the residual: a ResidualLayer input (HOLD .. RES_HELD) must not span
     // the RES_EXT stage, and a stage adds at most one residual
     if ((S.flags & X2G_CHAIN_RES_EXT) && (S.flags & (X2G_CHAIN_HOLD | X2G_CHAIN_RES_HELD))) return X2G_EINVAL;
@@ -1984,16 +2046,29 @@ X2G_API int x2g_conv_proj_bwd_gate(const x2g_proj_grad* grads, int64_t rows, int
   a.R = rows;
   const unsigned grid = proj_grid(rows);
   const bool tw = grads[0].wt && grads[1].wt && grads[2].wt && grads[3].wt;
-  if (rbf_dim <= 6) {
-    if (tw)
-      conv_proj_bwd_gate_kernel<6, true><<<grid, kCThreads, 0, st>>>(a);
+  // no T-layout copy wanted at all: the instance without the copy code (a mixed set keeps the copies,
+  // the stores of the NULL ones dropped by an empty descriptor)
+  const bool tc = grads[0].g_t || grads[1].g_t || grads[2].g_t || grads[3].g_t;
+  auto launch = [&](auto nj, auto tw_, auto tc_) {
+    conv_proj_bwd_gate_kernel<decltype(nj)::value, decltype(tw_)::value, decltype(tc_)::value>
+        <<<grid, kCThreads, 0, st>>>(a);
+  };
+  auto pick_tc = [&](auto nj, auto tw_) {
+    if (tc)
+      launch(nj, tw_, std::true_type{});
     else
-      conv_proj_bwd_gate_kernel<6, false><<<grid, kCThreads, 0, st>>>(a);
-  } else if (tw) {
-    conv_proj_bwd_gate_kernel<8, true><<<grid, kCThreads, 0, st>>>(a);
-  } else {
-    conv_proj_bwd_gate_kernel<8, false><<<grid, kCThreads, 0, st>>>(a);
-  }
+      launch(nj, tw_, std::false_type{});
+  };
+  auto pick_tw = [&](auto nj) {
+    if (tw)
+      pick_tc(nj, std::true_type{});
+    else
+      pick_tc(nj, std::false_type{});
+  };
+  if (rbf_dim <= 6)
+    pick_tw(std::integral_constant<int, 6>{});
+  else
+    pick_tw(std::integral_constant<int, 8>{});
   const int rc = last_launch_status();
   if (rc || (flags & X2G_DEFER_SLAB_SUM)) return rc;
   x2g_slab_job sj{a.part_w, nullptr, dw_rbf, nullptr, static_cast<int64_t>(kCD) * rbf_dim, 0,
@@ -2070,6 +2145,9 @@ static int flat_launch(const x2g_tiled_job* jobs, const int64_t* rows, int32_t n
     if (!J.dy_t || !J.x_t || !J.dw) return X2G_EINVAL;
     if (!al16(J.dy_t) || !al16(J.x_t)) return X2G_EUNSUPPORTED;
     if (J.ld < 0 || (J.ld > 0 && (J.cols < 1 || J.cols > kCD || J.cols > J.ld))) return X2G_EINVAL;
+    if (J.layout & ~(X2G_TILED_DY_ROWMAJOR | X2G_TILED_X_ROWMAJOR)) return X2G_EINVAL;
+    a.layout[j] = J.layout;
+    a.rows[j] = static_cast<int>(rows[j]);  // < 2^22 (flat_tiles)
     int lo, n;
     flat_span(a.tile0[j], a.tile0[j + 1], a.total, G, lo, n);
     a.in_t[j] = J.x_t;
@@ -2142,6 +2220,7 @@ X2G_API int x2g_tiled_wgrad(const x2g_tiled_job* jobs, int32_t num_jobs, int64_t
     const x2g_tiled_job& J = jobs[j];
     if (!J.dy_t || !J.x_t || !J.dw) return X2G_EINVAL;
     if (!al16(J.dy_t) || !al16(J.x_t)) return X2G_EUNSUPPORTED;
+    if (J.layout) return X2G_EUNSUPPORTED;  // row-major operands: the flat launch only
     a.in_t[j] = J.x_t;
     a.dz_t[j] = J.dy_t;
     a.part_w[j] = reinterpret_cast<float*>(static_cast<char*>(workspace) + per * j);

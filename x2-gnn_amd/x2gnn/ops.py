@@ -801,7 +801,11 @@ class _ReadoutMLPs(torch.autograd.Function):
             def wt(g, i):
                 return WT[g, i].data_ptr() if grad else None
 
-            stages = [(ChainStage * 2)(ChainStage(_dp(W1[g]), _dp(B1[g]), _dp(z1[g]), None, wt(g, 0), CHAIN_SILU),
+            # (as _ChainFn: the flat launch reads each readout's input rows row-major, no T plane 0)
+            ctx.rm0 = WGRAD_X_ROWMAJOR and grad and all(grad_sink(p) is not None
+                                                        for p in (*W1, *B1, *W2, *B2) if p is not None)
+            f0 = CHAIN_SILU | (CHAIN_IN0_ROWMAJOR if ctx.rm0 else 0)
+            stages = [(ChainStage * 2)(ChainStage(_dp(W1[g]), _dp(B1[g]), _dp(z1[g]), None, wt(g, 0), f0),
                                        ChainStage(_dp(W2[g]), _dp(B2[g]), _dp(z2[g]), _dp(h2[g]), wt(g, 1), CHAIN_SILU))
                       for g in range(G)]
             jobs = (ChainFwdJob * G)(*[ChainFwdJob(_dp(xs[g]), None, ctypes.addressof(stages[g]),
@@ -811,7 +815,7 @@ class _ReadoutMLPs(torch.autograd.Function):
                                       for g in range(G)])
             out = _head_fwd(heads, G, R, D, pool, f32, st)
             if grad:
-                ctx.save_for_backward(*h2, *z1, *z2, WT, in_t)
+                ctx.save_for_backward(*h2, *z1, *z2, WT, in_t, *(xs if ctx.rm0 else ()))
             ctx.G, ctx.params = G, params
             return out
         h1 = [torch.empty(R, D, **f32) for _ in range(G)]
@@ -871,7 +875,8 @@ class _ReadoutMLPs(torch.autograd.Function):
             call("x2g_chain_bwd_batch", jobs, G, 2, R, D, st)
             pg = []
             for g in range(G):
-                dws, dbs = chain_wgrad(in_t[g], dz_t[g], R, [W1[g], W2[g]], [B1[g], B2[g]])
+                dws, dbs = chain_wgrad(in_t[g], dz_t[g], R, [W1[g], W2[g]], [B1[g], B2[g]],
+                                       x0=saved[3 * G + 2 + g] if ctx.rm0 else None)
                 pg += [dws[0], dbs[0], dws[1], dbs[1]]
                 pg += [None if acc3 else dw3[g].view_as(W3[g]), None if acc3 else db3[g]]
             return (None, None, *dfeat, *pg)
@@ -1535,6 +1540,7 @@ def residual_layer(x, w0, b0, w1, b1):
 
 CHAIN_SILU, CHAIN_HOLD, CHAIN_RES_HELD, CHAIN_RES_EXT = 1, 2, 4, 8  # X2G_CHAIN_* (include/x2g.h)
 CHAIN_RES_ACCUM = 16  # backward only
+CHAIN_IN0_ROWMAJOR = 32  # forward only, stage 0: no T plane 0 (the weight gradient reads the input row-major)
 CHAIN_MAX_STAGES = 8
 
 
@@ -1584,10 +1590,11 @@ def wgrad_batched(dys, xs, weights, biases):
     return dws, dbs
 
 
-def chain_wgrad(in_t, dz_t, R, weights, biases):
-    """Weight / bias gradients of every chain stage from the T-layout operands (x2g_chain_wgrad);
-    bucket-backed parameters are summed into the bucket (Nones returned for them), slab sums
-    deferred inside ``deferred_wgrad()``."""
+def chain_wgrad(in_t, dz_t, R, weights, biases, x0=None):
+    """Weight / bias gradients of every chain stage from the T-layout operands (x2g_chain_wgrad, or
+    tiled jobs of the flat launch inside ``deferred_wgrad()`` or with ``x0``); bucket-backed parameters
+    are summed into the bucket (Nones returned for them), slab sums deferred inside ``deferred_wgrad()``.  ``x0``: the chain's input, row-major [R, D], when the forward
+    ran with CHAIN_IN0_ROWMAJOR (plane 0 of ``in_t`` is then unwritten and stage 0 reads ``x0``)."""
     n = len(weights)
     D = weights[0].shape[1]
     dev = in_t.device
@@ -1596,11 +1603,20 @@ def chain_wgrad(in_t, dz_t, R, weights, biases):
     dws, rest = bufs[:n], iter(bufs[n:])
     dbs = [next(rest) if b is not None else None for b in biases]
     d = _defer() if acc else None
-    if d is not None:
+    if d is not None or x0 is not None:
         tf = in_t.shape[1]
-        _queue_tiled(d, R, [TiledJob(dz_t.data_ptr() + 4 * g * tf, in_t.data_ptr() + 4 * g * tf, _dp(dws[g]), _dp(dbs[g]),
-                                  0, 0) for g in range(n)], [in_t, dz_t])
-        return [None] * n, [None] * n
+        jobs = [TiledJob(dz_t.data_ptr() + 4 * g * tf, in_t.data_ptr() + 4 * g * tf, _dp(dws[g]), _dp(dbs[g]), 0, 0)
+                for g in range(n)]
+        if x0 is not None:
+            jobs[0] = TiledJob(dz_t.data_ptr(), x0.data_ptr(), _dp(dws[0]), _dp(dbs[0]), 0, 0, TILED_X_ROWMAJOR)
+        if d is not None:
+            # (the flat launch runs after this backward returned: x0 is kept alive with the T tensors)
+            _queue_tiled(d, R, jobs, [in_t, dz_t] + ([x0] if x0 is not None else []))
+            return [None] * n, [None] * n
+        _tiled_now(R, jobs, acc, dev)
+        if acc:
+            return [None] * n, [None] * n
+        return dws, dbs
     lib = _lib.load()
     ws_bytes = int(lib.x2g_chain_wgrad_workspace(R, D, n))
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
@@ -1617,8 +1633,10 @@ class _ChainFn(torch.autograd.Function):
     """A chain of D x D Linear stages on the same rows in ONE kernel (x2g_chain_fwd, csrc/chain.hip):
     stage s computes z_s = in_s W_s^T + b_s, out_s = act(z_s) (+ the held ResidualLayer input or
     the external residual), in_{s+1} = out_s.  Backward: one kernel for every stage's data gradient
-    (x2g_chain_bwd, residual gradients folded in registers) + one weight-gradient launch over the
-    stage inputs and dz that both kernels leave in the tiled-transposed layout (x2g_chain_wgrad)."""
+    (x2g_chain_bwd, residual gradients folded in registers) + the weight gradients over the stage
+    inputs and dz that both kernels leave in the tiled-transposed layout: x2g_chain_wgrad for plain
+    parameters; for bucket-backed ones (a training step) tiled jobs of the flat launch, whose stage 0
+    reads the chain's row-major input (CHAIN_IN0_ROWMAJOR: the forward then writes no T plane 0)."""
 
     @staticmethod
     def forward(ctx, x, res, flags, ln, *params):
@@ -1637,8 +1655,14 @@ class _ChainFn(torch.autograd.Function):
         # for the backward: W^T of every stage, and every stage input in the T layout
         WT = torch.empty(n, D, D, **f32) if grad else None
         in_t = torch.empty(n, tf, **f32) if grad else None
+        # The chain's input stays row-major for the backward anyway (xn on the LayerNorm path, else x2), so
+        # when the weight gradients will be tiled jobs of the flat launch (bucket-backed parameters: what a
+        # training step has) stage 0's reads it there and the kernel writes no T plane 0.  x2g_chain_wgrad
+        # (plain parameters) reads contiguous T planes and keeps plane 0.
+        ctx.rm0 = WGRAD_X_ROWMAJOR and grad and all(grad_sink(p) is not None for p in params if p is not None)
+        fl = [flags[i] | (CHAIN_IN0_ROWMAJOR if ctx.rm0 and i == 0 else 0) for i in range(n)]
         st = (ChainStage * n)(*[ChainStage(_dp(W[i]), _dp(B[i]), _dp(zs[i]), _dp(y) if i == n - 1 else None,
-                                           None if WT is None else WT[i].data_ptr(), flags[i]) for i in range(n)])
+                                           None if WT is None else WT[i].data_ptr(), fl[i]) for i in range(n)])
         ctx.ln = ln is not None
         if ln is None:
             call("x2g_chain_fwd", ptr(x2), ptr(r2), st, n, R, D, ptr(in_t), stream_ptr())
@@ -1652,7 +1676,8 @@ class _ChainFn(torch.autograd.Function):
             ln_saved = (xn, rstd, rowptr)
             ctx.ln_segments = G
         if grad:
-            ctx.save_for_backward(*W, *[z if z is not None else x2 for z in zs], WT, in_t, *ln_saved)
+            ctx.save_for_backward(*W, *[z if z is not None else x2 for z in zs], WT, in_t, *ln_saved,
+                                  *((x2,) if ctx.rm0 and ln is None else ()))
         ctx.flags, ctx.params, ctx.has_res = tuple(flags), params, res is not None
         ctx.fan_res = _fan_of(res)
         return y
@@ -1701,7 +1726,8 @@ class _ChainFn(torch.autograd.Function):
                  stream_ptr())
             dx = dxp
         ws, bs = ctx.params[0::2], ctx.params[1::2]
-        dws, dbs = chain_wgrad(in_t, dz_t, R, ws, bs)
+        # (rm0: stage 0's input is the saved row-major one, xn or x2, both right after in_t in `saved`)
+        dws, dbs = chain_wgrad(in_t, dz_t, R, ws, bs, x0=saved[2 * n + 2] if ctx.rm0 else None)
         grads = []
         for i in range(n):
             grads += [dws[i], dbs[i]]
@@ -1937,9 +1963,28 @@ def featurize(x, env, lin1, lin2):
 
 
 class TiledJob(ctypes.Structure):
-    """x2g_tiled_job."""
+    """x2g_tiled_job.  ``layout``: TILED_DY_ROWMAJOR | TILED_X_ROWMAJOR (0: both operands in the T layout)."""
     _fields_ = [("dy_t", ctypes.c_void_p), ("x_t", ctypes.c_void_p), ("dw", ctypes.c_void_p), ("db", ctypes.c_void_p),
-                ("ld", ctypes.c_int32), ("cols", ctypes.c_int32)]
+                ("ld", ctypes.c_int32), ("cols", ctypes.c_int32), ("layout", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+TILED_DY_ROWMAJOR, TILED_X_ROWMAJOR = 1, 2  # X2G_TILED_*_ROWMAJOR
+
+# The weight gradients' x operands that exist row-major anyway (the projections' x, the chains' input) are
+# read there, and no T-layout copy of them is written.  False: the forwards write those copies (x_t, T
+# plane 0) as before.  A constant like the switches above (an A/B script or a test sets it).
+WGRAD_X_ROWMAJOR = True
+
+
+def _tiled_now(R, jobs, acc, dev):
+    """The given x2g_tiled_jobs in one flat launch of their own, slab sums included (no deferral open:
+    the path of jobs with a row-major operand, which x2g_tiled_wgrad / x2g_chain_wgrad do not take)."""
+    lib = _lib.load()
+    n = len(jobs)
+    ws_bytes = int(lib.x2g_tiled_wgrad_flat_workspace(R, 128, n))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    call("x2g_tiled_wgrad_flat", (TiledJob * n)(*jobs), n, R, 128, ACCUM_WGRAD if acc else 0, None, ptr(ws), ws_bytes,
+         stream_ptr())
 
 
 class Proj(ctypes.Structure):
@@ -1952,10 +1997,13 @@ class ProjGrad(ctypes.Structure):
     _fields_ = [("g", ctypes.c_void_p), ("w", ctypes.c_void_p), ("wt", ctypes.c_void_p), ("g_t", ctypes.c_void_p)]
 
 
-def tiled_wgrad(dy_ts, x_ts, R, weights, biases):
-    """Weight / bias gradients of D x D Linear layers from T-layout operands (x2g_tiled_wgrad), one
-    job per layer; bucket-backed parameters are summed into the bucket (Nones returned), slab sums
-    deferred inside ``deferred_wgrad()``."""
+def tiled_wgrad(dy_ts, x_ts, R, weights, biases, layouts=None):
+    """Weight / bias gradients of D x D Linear layers, one job per layer; bucket-backed parameters are
+    summed into the bucket (Nones returned).  Inside ``deferred_wgrad()`` the jobs are queued for its flat
+    launch and the slab sums deferred.  Otherwise: all operands in the T layout -> x2g_tiled_wgrad;
+    ``layouts`` (per job TILED_*_ROWMAJOR bits, operands given as row-major [R, D] tensors) -> a flat
+    launch of their own (x2g_tiled_wgrad_flat: x2g_tiled_wgrad takes T operands only; another row split,
+    so fp32 rounding differs from it)."""
     n = len(weights)
     D = weights[0].shape[1]
     dev = dy_ts[0].device
@@ -1964,10 +2012,16 @@ def tiled_wgrad(dy_ts, x_ts, R, weights, biases):
     dws, rest = bufs[:n], iter(bufs[n:])
     dbs = [next(rest) if b is not None else None for b in biases]
     d = _defer() if acc else None
-    if d is not None:
-        _queue_tiled(d, R, [TiledJob(_dp(dy_ts[g]), _dp(x_ts[g]), _dp(dws[g]), _dp(dbs[g]), 0, 0) for g in range(n)],
-                     list(dy_ts) + list(x_ts))
-        return [None] * n, [None] * n
+    lay = layouts if layouts is not None else [0] * n
+    if d is not None or any(lay):
+        jobs = [TiledJob(_dp(dy_ts[g]), _dp(x_ts[g]), _dp(dws[g]), _dp(dbs[g]), 0, 0, lay[g]) for g in range(n)]
+        if d is not None:
+            _queue_tiled(d, R, jobs, list(dy_ts) + list(x_ts))
+            return [None] * n, [None] * n
+        _tiled_now(R, jobs, acc, dev)
+        if acc:
+            return [None] * n, [None] * n
+        return dws, dbs
     lib = _lib.load()
     ws_bytes = int(lib.x2g_tiled_wgrad_workspace(R, D, n))
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
@@ -2033,30 +2087,30 @@ class _ConvProjFusedFn(torch.autograd.Function):
         lib = _lib.load()
         tf = int(lib.x2g_chain_t_floats(E, D))
         WT = torch.empty(4, D, D, **f32) if grad else None
-        x_t = torch.empty(tf, **f32) if grad else None
+        # x_src exists only inside the kernel, so its T-layout copy is kept for dW_k / dW_v; x is saved
+        # row-major anyway and the weight gradient reads it there (no x_t)
         xs_t = torch.empty(tf, **f32) if grad else None
+        x_t = torch.empty(tf, **f32) if grad and not WGRAD_X_ROWMAJOR else None
         proj = (Proj * 4)(*[Proj(_dp(W[i]), _dp(B[i]), _dp(outs[i]), None if WT is None else WT[i].data_ptr())
                             for i in range(4)])
         call("x2g_conv_proj_fwd", ptr(x2), ptr(rbf2), rbf2.shape[1], ptr(Wr), proj, E, D, ptr(x_t), ptr(xs_t),
              stream_ptr())
         if grad:
-            ctx.save_for_backward(x2, rbf2, Wr, *W, WT, x_t, xs_t)
+            ctx.save_for_backward(x2, rbf2, Wr, *W, WT, xs_t, x_t)
         ctx.params = (wr, wq, bq, wk, bk, wv, bv, ws, bs)
         ctx.fan_x, ctx.fan_r = _fan_of(x), _fan_of(rbf)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, gq, gk, gv, gskip):
-        x2, rbf2, Wr, Wq, Wk, Wv, Ws, WT, x_t, xs_t = ctx.saved_tensors
+        x2, rbf2, Wr, Wq, Wk, Wv, Ws, WT, xs_t, x_t = ctx.saved_tensors
         wr, wq, bq, wk, bk, wv, bv, ws, bs = ctx.params
         E, D = x2.shape
         f32 = dict(dtype=torch.float32, device=x2.device)
         g = [_f32(t) if t is not None else torch.zeros(E, D, **f32) for t in (gq, gk, gv, gskip)]
-        tf = x_t.shape[0]
-        g_t = torch.empty(4, tf, **f32)
         W = (Wq, Wk, Wv, Ws)
-        grads = (ProjGrad * 4)(*[ProjGrad(_dp(g[i]), _dp(W[i]), WT[i].data_ptr(), g_t[i].data_ptr())
-                                 for i in range(4)])
+        # no T-layout copies of the four gradients (g_t NULL): the weight gradient reads g itself
+        grads = (ProjGrad * 4)(*[ProjGrad(_dp(g[i]), _dp(W[i]), WT[i].data_ptr(), None) for i in range(4)])
         first_x = first_r = True
         if ctx.fan_x is not None:  # dx goes into (or adds onto) the layer input's fan-in buffer
             dx, first_x = ctx.fan_x.take((E, D), x2.device)
@@ -2070,8 +2124,12 @@ class _ConvProjFusedFn(torch.autograd.Function):
         gx, grbf, dwr = _conv_proj_bwd_gate(grads, x2, rbf2, Wr, wr, dx, first_x, need_rbf, drbf_out, first_r)
         gx = gx if first_x else None
         grbf = grbf if first_r else None
-        dws, dbs = tiled_wgrad([g_t[0], g_t[1], g_t[2], g_t[3]], [x_t, xs_t, xs_t, x_t], E, [wq, wk, wv, ws],
-                               [bq, bk, bv, bs])
+        # dy = g (row-major) for all four; x = x2 (row-major) for q and skip, the T-layout x_src for k and v.
+        # g and x2 go on the deferral's keep list: the flat launch reads them after this backward returned.
+        xo = x2 if x_t is None else x_t
+        lx = TILED_DY_ROWMAJOR | (TILED_X_ROWMAJOR if x_t is None else 0)
+        dws, dbs = tiled_wgrad(g, [xo, xs_t, xs_t, xo], E, [wq, wk, wv, ws], [bq, bk, bv, bs],
+                               layouts=[lx, TILED_DY_ROWMAJOR, TILED_DY_ROWMAJOR, lx])
         return (gx, (grbf if need_rbf else None), dwr, dws[0], dbs[0], dws[1], dbs[1], dws[2], dbs[2], dws[3],
                 dbs[3])
 
