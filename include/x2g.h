@@ -139,6 +139,36 @@ int x2g_batch_meta(const int64_t* edge_index, const int64_t* x, const int64_t* b
                    int32_t* dst_type, int32_t* atom_type, int32_t* line_ptr, int32_t* mol_ptr, int32_t* atom_rowptr,
                    int64_t* info, void* stream);
 
+/* One training batch assembled on the device from a dataset that lives there (x2gnn.DeviceDataset): what
+ * data.collate and _add_device_indices make on the host, gathered from the resident tensors in one launch.
+ * The dataset is PyG's InMemoryDataset layout, every molecule's tensors concatenated: x_all (int64 [N_all]),
+ * atom_pos_all (f32 [N_all, 3]), edge_index_all (int64 [2, E_all], MOLECULE-LOCAL atom ids; row 1 starts
+ * edge_row_stride elements after row 0), edge_attr_all (f32 [E_all, num_features]; NULL with edge_attr NULL =
+ * no edge features), y_all (f32 [M]; NULL with y NULL) and trips_all (int64 [M], triplets per molecule; NULL
+ * with mol_trips NULL).  The batch is num_mols molecules in any order, repeats allowed, given by one device
+ * block of int64
+ *   offsets = [source atom start (B) | source edge start (B) | molecule id (B) |
+ *              destination atom offsets (B + 1) | destination edge offsets (B + 1)],   B = num_mols,
+ * the last two ascending from 0 to num_nodes / num_edges; the caller guarantees that the starts and ids lie
+ * inside the dataset and that a molecule's local atom ids lie inside it (nothing is read back to check).
+ * Outputs, caller-allocated: x (int64 [N]), atom_pos (f32 [N, 3]), batch (int64 [N]), ptr (int64 [B + 1]),
+ * edge_index (int64 [2, E], shifted by the running atom count), edge_attr (f32 [E, num_features]), edge_num
+ * (int64 [B]), y (f32 [B]), the int32 forms edge_src / edge_dst / src_type / dst_type ([E]), atom_type ([N]),
+ * mol_ptr / line_ptr ([B + 1]) and mol_trips (int64 [B]).  Every element has one writer (no atomics).
+ * The edge_attr move is the traffic: chunks of the destination, each walking the molecule slabs it overlaps
+ * and copying 16 bytes per lane where source and destination agree mod 16, else 8 (a 338-float row is
+ * 8 * 169 bytes: an odd edge count leaves later slabs 8-byte aligned only), else 4; nothing is assumed beyond
+ * float alignment.  Offsets into the dataset and into the batch are 64-bit throughout.
+ * num_mols = 0 (then num_nodes = num_edges = 0) launches nothing; num_edges = 0 still writes the atom and
+ * molecule outputs.  N, E or B >= 2^31 (the int32 forms): X2G_EUNSUPPORTED, before anything is touched. */
+int x2g_batch_assemble(const int64_t* x_all, const float* atom_pos_all, const int64_t* edge_index_all,
+                       int64_t edge_row_stride, const float* edge_attr_all, int32_t num_features,
+                       const float* y_all, const int64_t* trips_all, const int64_t* offsets, int64_t num_mols,
+                       int64_t num_nodes, int64_t num_edges, int64_t* x, float* atom_pos, int64_t* batch,
+                       int64_t* ptr, int64_t* edge_index, float* edge_attr, int64_t* edge_num, float* y,
+                       int32_t* edge_src, int32_t* edge_dst, int32_t* src_type, int32_t* dst_type,
+                       int32_t* atom_type, int32_t* mol_ptr, int32_t* line_ptr, int64_t* mol_trips, void* stream);
+
 /* ---------------------------------------------------------------- basis (featurisation) */
 
 /* rbf_env[e, l*R+n] = env(d_e) * N_ln j_l(z_ln d_e/cutoff)   (l < num_spherical, n < R = num_radial)

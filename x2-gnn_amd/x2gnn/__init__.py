@@ -6,6 +6,7 @@ Device side: ``libx2g.so`` (hand-written gfx950 HIP kernels behind the C ABI in
 ``include/x2g.h``), loaded through :mod:`x2gnn._lib`.
 """
 from .data import Batch, Data, collate, molecule_to_data
+from .device_dataset import DeviceDataset
 from .layers import AtomWise, EmbeddingBlock, F_B_2D, MolWise, RadialBasis, ResidualLayer, poly_envelop
 from .model import LayerNorm, SBFTransformer, SBFTransformerGlobal
 from .plan import GraphPlan
@@ -13,7 +14,7 @@ from .sbftransformer_conv import SBFTransformerConv
 from .xgnn import xgnn_poly, xgnn_poly_global
 
 __all__ = [
-    "AtomWise", "Batch", "Data", "EmbeddingBlock", "F_B_2D", "GraphPlan", "LayerNorm", "MolWise", "RadialBasis",
-    "ResidualLayer", "SBFTransformer", "SBFTransformerConv", "SBFTransformerGlobal", "collate", "molecule_to_data",
+    "AtomWise", "Batch", "Data", "DeviceDataset", "EmbeddingBlock", "F_B_2D", "GraphPlan", "LayerNorm", "MolWise",
+    "RadialBasis", "ResidualLayer", "SBFTransformer", "SBFTransformerConv", "SBFTransformerGlobal", "collate", "molecule_to_data",
     "poly_envelop", "xgnn_poly", "xgnn_poly_global",
 ]

@@ -1,0 +1,269 @@
+"""A dataset that lives on the GPU: every training batch is assembled there (x2g_batch_assemble).
+
+The reference's loop collates a fresh batch on the host every step and copies it over (trainer.py:37-48);
+on this card that is the slowest part of a step — the 28 MB ``edge_attr`` [E, 338] concatenation, its
+worker-to-parent hand-off and its H2D copy.  All of QM9's ``edge_attr`` is 28-50 GB against 288 GB of HBM,
+so :class:`DeviceDataset` keeps the collated dataset resident (PyG's ``InMemoryDataset`` layout: concatenated
+tensors, per-molecule slices, ``edge_index`` not incremented) and builds a batch from a list of molecule
+indices with one ragged-gather launch.  Per batch the host touches O(B) integers (cached per-molecule sizes)
+and uploads one block of 5 B + 2 int64; nothing is read back.
+
+``batch(indices)`` returns the same ``Batch``, key for key, as ``collate([mols[i] for i in indices]).to(device)``
+gives with ``data.HOST_SCHEDULE`` False: the center kernels' schedule is made on the device by the plan.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .data import Batch
+
+_RING = 4  # pinned staging slots for the offset block: a slot is rewritten only after its copy has finished
+
+
+def molecule_stats(nodes, edges, edge_index):
+    """Per-molecule (triplets int64 [M], max out-degree int64 [M], symmetric bool [M]) of a concatenated dataset
+    with molecule-local ``edge_index`` (int64 [2, E_all]), vectorised over the whole dataset: equal to
+    ``synth.triplet_count``, ``np.bincount(src).max()`` and ``data._is_symmetric`` called molecule by molecule
+    (which takes minutes at 130k molecules).  Raises ValueError when a local atom id lies outside its molecule."""
+    nodes = np.asarray(nodes, dtype=np.int64)
+    edges = np.asarray(edges, dtype=np.int64)
+    ei = np.asarray(edge_index, dtype=np.int64).reshape(2, -1)
+    M, n_all, e_all = len(nodes), int(nodes.sum()), int(edges.sum())
+    if ei.shape[1] != e_all:
+        raise ValueError(f"edge_index has {ei.shape[1]} edges, the per-molecule counts sum to {e_all}")
+    if e_all == 0:
+        return np.zeros(M, np.int64), np.zeros(M, np.int64), np.ones(M, bool)
+    atom_start = np.concatenate([[0], np.cumsum(nodes)])[:-1]
+    mol = np.repeat(np.arange(M, dtype=np.int64), edges)  # the molecule of each edge
+    if bool(((ei < 0) | (ei >= nodes[mol])).any()):
+        raise ValueError("edge_index must hold molecule-local atom ids inside each molecule")
+    src, dst = ei[0] + atom_start[mol], ei[1] + atom_start[mol]  # dataset-wide atom ids: keys never cross molecules
+    deg = np.bincount(src, minlength=n_all)
+    key, rev = src * n_all + dst, dst * n_all + src
+    order = np.argsort(key, kind="stable")  # (molecule-major: a molecule's atoms are consecutive)
+    skey = key[order]
+    pos = np.searchsorted(skey, rev)
+    has_rev = skey[np.minimum(pos, e_all - 1)] == rev  # np.isin(rev, key), on the sort the duplicate test needs
+    # triplets: sum over e = (a->b) of |N_out(b) \ {a}|
+    trips = np.bincount(mol, weights=(deg[dst] - has_rev).astype(np.float64), minlength=M).astype(np.int64)
+    owner = np.repeat(np.arange(M, dtype=np.int64), nodes)
+    max_deg = np.zeros(M, np.int64)
+    np.maximum.at(max_deg, owner, deg)
+    # symmetric: no directed edge twice (data._is_symmetric sends such a multigraph down the generic path), and
+    # every reverse present — with distinct edges that makes the forward and reverse sets equal
+    dup = np.bincount(mol[order][1:][skey[1:] == skey[:-1]], minlength=M) > 0
+    missing = np.bincount(mol[~has_rev], minlength=M) > 0
+    return trips, max_deg, ~(dup | missing)
+
+
+class DeviceDataset:
+    """The collated dataset on one GPU; see the module docstring.
+
+    Host caches (numpy, one entry per molecule): ``nodes``, ``edges``, ``triplets``, ``max_degree``,
+    ``symmetric`` and the prefix sums ``atom_start`` / ``edge_start`` ([M + 1]).  Device tensors: ``x`` int64
+    [N_all], ``atom_pos`` f32 [N_all, 3], ``edge_index`` int64 [2, E_all] (molecule-local), ``edge_attr`` f32
+    [E_all, F] or None, ``y`` f32 [M], ``mol_trips`` int64 [M]."""
+
+    def __init__(self, mols, device):
+        """``mols``: molecule dicts as :func:`x2gnn.data.collate` takes them."""
+        M = len(mols)
+        nodes = np.fromiter((len(m["x"]) for m in mols), dtype=np.int64, count=M)
+        edges = np.fromiter((int(m["edge_num"]) for m in mols), dtype=np.int64, count=M)
+
+        def cat(parts, dtype, tail):
+            return np.concatenate(parts) if parts else np.zeros((0,) + tail, dtype)
+
+        x = cat([np.asarray(m["x"], dtype=np.int64).reshape(-1) for m in mols], np.int64, ())
+        pos = cat([np.asarray(m["atom_pos"], dtype=np.float32).reshape(-1, 3) for m in mols], np.float32, (3,))
+        ei = (np.concatenate([np.asarray(m["edge_index"], dtype=np.int64).reshape(2, -1) for m in mols], axis=1)
+              if M else np.zeros((2, 0), np.int64))
+        attr = (np.concatenate([np.asarray(m["edge_attr"], dtype=np.float32) for m in mols])
+                if M and "edge_attr" in mols[0] else None)
+        y = np.array([float(m.get("y", 0.0)) for m in mols], dtype=np.float32)
+        self._init(nodes, edges, x, pos, ei, attr, y, device)
+
+    @classmethod
+    def from_collated(cls, dataset, device):
+        """From a :class:`x2gnn.datasets.CollatedDataset` (a PyG ``InMemoryDataset`` processed file) after
+        ``prepare_target``, so that ``y`` is one value per molecule."""
+        st, sl = dataset.data._store, dataset.slices
+        M = len(dataset)
+        y = st["y"]
+        if y.dim() != 1 or int(y.shape[0]) != M:
+            raise ValueError(f"y must be [M] = [{M}] (run datasets.prepare_target first), got {tuple(y.shape)}")
+        nodes = np.diff(sl["x"].numpy().astype(np.int64))
+        edges = np.diff(sl["edge_index"].numpy().astype(np.int64))
+        attr = st["edge_attr"].to(torch.float32).numpy() if "edge_attr" in st else None
+        self = cls.__new__(cls)
+        self._init(nodes, edges, st["x"].to(torch.int64).numpy().reshape(-1),
+                   st["atom_pos"].to(torch.float32).numpy().reshape(-1, 3),
+                   st["edge_index"].to(torch.int64).numpy().reshape(2, -1), attr,
+                   y.to(torch.float32).numpy(), device)
+        return self
+
+    def _init(self, nodes, edges, x, pos, ei, attr, y, device):
+        self.device = torch.device(device)
+        self.nodes, self.edges = nodes, edges
+        if int(nodes.sum()) != len(x) or len(pos) != len(x) or len(y) != len(nodes):
+            raise ValueError("per-molecule sizes do not match the concatenated tensors")
+        if attr is not None and (attr.ndim != 2 or attr.shape[0] != ei.shape[1]):
+            raise ValueError(f"edge_attr has shape {attr.shape} for {ei.shape[1]} edges")
+        self.triplets, self.max_degree, self.symmetric = molecule_stats(nodes, edges, ei)
+        self.atom_start = np.concatenate([[0], np.cumsum(nodes)]).astype(np.int64)
+        self.edge_start = np.concatenate([[0], np.cumsum(edges)]).astype(np.int64)
+        self.num_features = int(attr.shape[1]) if attr is not None else 0
+
+        def up(a):  # the one H2D copy of each concatenated tensor
+            return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+
+        self.x, self.atom_pos, self.edge_index, self.y = up(x), up(pos), up(ei), up(y)
+        self.edge_attr = up(attr) if attr is not None else None
+        self.mol_trips = up(self.triplets)
+        self._stage = None  # _RING x (pinned int64 buffer, event of the last copy out of it), made on first use
+        self._slot = 0
+        self._debug_fill = None  # tests: (int, float) sentinels written over every output before the launch
+
+    def __len__(self):
+        return int(self.nodes.shape[0])
+
+    # ------------------------------------------------------------------------------------------ one batch
+    def _indices(self, indices):
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        M = len(self)
+        bad = (idx < -M) | (idx >= M)
+        if bad.any():
+            raise IndexError(f"molecule index {int(idx[bad][0])} out of range for a dataset of {M}")
+        return np.where(idx < 0, idx + M, idx)
+
+    def _upload(self, block):
+        """The offset block on the device: through a pinned staging slot, non-blocking.  The ring's slot is
+        rewritten only once the copy last issued from it has finished (an event; _RING batches later it has).
+        Under graph capture no event is waited for or recorded (neither is legal there); the captured copy reads
+        the slot when the graph is replayed, so such a graph replays the batch only until the ring comes round."""
+        n = int(block.shape[0])
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._stage is None or self._stage[0][0].shape[0] < n:
+            # every slot at once, so that a warmed-up caller allocates nothing later (e.g. under graph capture)
+            self._stage = [(torch.empty(max(n, 1024), dtype=torch.int64, pin_memory=True), torch.cuda.Event())
+                           for _ in range(_RING)]
+        slot = self._stage[self._slot]
+        if not capturing:
+            slot[1].synchronize()  # (returns at once for an event never recorded)
+        self._slot = (self._slot + 1) % _RING
+        slot[0][:n].numpy()[:] = block
+        dev = torch.empty(n, dtype=torch.int64, device=self.device)
+        dev.copy_(slot[0][:n], non_blocking=True)
+        if not capturing:
+            slot[1].record(torch.cuda.current_stream(self.device))
+        return dev
+
+    def _assemble(self, idx, atoms_only=False):
+        """Launch x2g_batch_assemble for the (validated) molecule indices; returns the outputs by name and the
+        per-molecule host sizes.  ``atoms_only``: the atom and molecule outputs alone (no edges)."""
+        from ._lib import call, ptr, stream_ptr
+
+        B = int(idx.shape[0])
+        nodes = self.nodes[idx]
+        edges = np.zeros(B, np.int64) if atoms_only else self.edges[idx]
+        N, E = int(nodes.sum()), int(edges.sum())
+        block = np.empty(5 * B + 2, np.int64)
+        block[:B] = self.atom_start[idx]
+        block[B:2 * B] = self.edge_start[idx]
+        block[2 * B:3 * B] = idx
+        block[3 * B] = 0
+        np.cumsum(nodes, out=block[3 * B + 1:4 * B + 1])
+        block[4 * B + 1] = 0
+        np.cumsum(edges, out=block[4 * B + 2:])
+        dev = self.device
+        F = 0 if atoms_only else self.num_features
+        # fresh per call (the eager step's autograd holds on to a batch past the next one): one allocation per
+        # dtype, the outputs are views of it; edge_attr on its own (16-byte aligned whatever E and N are)
+        i64 = torch.empty(2 * N + (B + 1) + 2 * E + 2 * B, dtype=torch.int64, device=dev)
+        i32 = torch.empty(4 * E + N + 2 * (B + 1), dtype=torch.int32, device=dev)
+        f32 = torch.empty(3 * N + B, dtype=torch.float32, device=dev)
+        attr = torch.empty((E, F), dtype=torch.float32, device=dev) if F else None
+        if self._debug_fill is not None:
+            i64.fill_(self._debug_fill[0])
+            i32.fill_(self._debug_fill[0])
+            f32.fill_(self._debug_fill[1])
+            if attr is not None:
+                attr.fill_(self._debug_fill[1])
+        x, batch, p, ei, edge_num, trips = torch.split(i64, [N, N, B + 1, 2 * E, B, B])
+        src, dst, src_t, dst_t, atom_t, mol_ptr, line_ptr = torch.split(i32, [E, E, E, E, N, B + 1, B + 1])
+        pos, y = torch.split(f32, [3 * N, B])
+        off = self._upload(block)
+        call("x2g_batch_assemble", ptr(self.x), ptr(self.atom_pos), ptr(self.edge_index),
+             int(self.edge_index.shape[1]), ptr(self.edge_attr) if F else None, F, ptr(self.y), ptr(self.mol_trips),
+             ptr(off), B, N, E, ptr(x), ptr(pos), ptr(batch), ptr(p), ptr(ei), ptr(attr), ptr(edge_num), ptr(y),
+             ptr(src), ptr(dst), ptr(src_t), ptr(dst_t), ptr(atom_t), ptr(mol_ptr), ptr(line_ptr), ptr(trips),
+             stream_ptr(dev))
+        out = {"x": x, "atom_pos": pos.view(N, 3), "edge_index": ei.view(2, E), "edge_attr": attr,
+               "edge_num": edge_num, "y": y, "batch": batch, "ptr": p, "_x2g_edge_src": src, "_x2g_edge_dst": dst,
+               "_x2g_mol_ptr": mol_ptr, "_x2g_line_ptr": line_ptr, "_x2g_dst_type": dst_t, "_x2g_src_type": src_t,
+               "_x2g_atom_type": atom_t, "_x2g_mol_trips": trips}
+        return out, nodes, edges
+
+    def batch(self, indices) -> Batch:
+        """The collated batch of molecules ``indices`` (any sequence, any order, repeats allowed) on the device.
+        An index outside the dataset raises IndexError before anything is launched."""
+        idx = self._indices(indices)
+        if idx.shape[0] == 0:
+            raise ValueError("a batch needs at least one molecule")
+        out, nodes, edges = self._assemble(idx)
+        b = Batch()
+        object.__setattr__(b, "_meta", {"nodes": nodes, "edges": edges, "triplets": self.triplets[idx]})
+        st = b._store
+        for k in ("x", "atom_pos", "edge_index", "edge_attr", "edge_num", "y", "batch", "ptr", "_x2g_edge_src",
+                  "_x2g_edge_dst", "_x2g_mol_ptr", "_x2g_line_ptr", "_x2g_dst_type", "_x2g_src_type",
+                  "_x2g_atom_type"):  # (data.collate's keys, in its order)
+            if out[k] is not None:
+                st[k] = out[k]
+        st["_x2g_symmetric"] = bool(self.symmetric[idx].all())
+        st["_x2g_mol_trips"] = out["_x2g_mol_trips"]
+        st["_x2g_max_mol_atoms"] = int(nodes.max())
+        st["_x2g_max_degree"] = int(self.max_degree[idx].max())
+        st["_x2g_device_schedule"] = True  # GraphPlan.from_atom_batch: ops.center_schedule, no O(N) host work
+        return b
+
+    def shard_batch(self, indices, world: int, rank: int):
+        """This rank's share of the global batch ``indices`` (``dist.collate_shard``'s device counterpart):
+        (local Batch, local molecule count, global molecule count), the shard from ``dist.shard_by_triplets``
+        over the cached triplet counts, the local batch carrying the global batch's atomic numbers
+        (``_x2g_count_z``: gathered by the same kernel's atom path)."""
+        from .dist import shard_by_triplets
+
+        idx = self._indices(indices)
+        mine = shard_by_triplets(self.triplets[idx], world)[rank]
+        b = self.batch(idx[mine])
+        b._store["_x2g_count_z"] = self._assemble(idx, atoms_only=True)[0]["x"]
+        return b, len(mine), int(idx.shape[0])
+
+    # ------------------------------------------------------------------------------------------ one epoch
+    def loader(self, batch_size, shuffle=True, seed=0, drop_last=False, indices=None):
+        """An iterable over one epoch of batches: a host permutation (seeded numpy generator) of ``indices``
+        (default: every molecule; e.g. a train / validation split), cut into ``batch_size`` pieces."""
+        return _Epoch(self, int(batch_size), shuffle, seed, drop_last, indices)
+
+
+class _Epoch:
+    def __init__(self, ds, batch_size, shuffle, seed, drop_last, indices):
+        if batch_size < 1:
+            raise ValueError("batch_size must be positive")
+        pool = np.arange(len(ds), dtype=np.int64) if indices is None else ds._indices(indices)
+        self.order = np.random.default_rng(seed).permutation(pool) if shuffle else pool
+        self.ds, self.batch_size, self.drop_last = ds, batch_size, drop_last
+
+    def index_lists(self):
+        """The epoch's batches as index arrays (what ``__iter__`` assembles)."""
+        n, bs = len(self.order), self.batch_size
+        stop = n - n % bs if self.drop_last else n
+        return [self.order[i:i + bs] for i in range(0, stop, bs)]
+
+    def __len__(self):
+        n, bs = len(self.order), self.batch_size
+        return n // bs if self.drop_last else (n + bs - 1) // bs
+
+    def __iter__(self):
+        for idx in self.index_lists():
+            yield self.ds.batch(idx)
