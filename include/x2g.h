@@ -283,7 +283,8 @@ int x2g_sbf_project_batch(const float* sbf, int64_t num_triplets, int32_t sbf_di
  *   a = softmax_dst(alpha) (max shift, /(sum+1e-16)), S_t = W_sbf sbf_t + b_sbf,
  *   out[e] = sum_{t in seg(e)} u_t*S_t*a_t,h + skip[e].
  * Saves alpha_raw[T,H], seg_max[E,H], seg_den[E,H] for the backward.
- * Compiled for H*C in {32,64,128,256}, C in {4,8,16,32} with C >= channels-per-lane, sbf_dim 42. */
+ * Compiled for H*C in {32,64,128,256}, C in {4,8,16,32} with C >= channels-per-lane, sbf_dim 42;
+ * any other shape is X2G_EUNSUPPORTED, for an empty batch (num_edges 0) too. */
 int x2g_sbf_attention_fwd(const float* q, const float* k, const float* v, const float* skip,
                           const float* edge, const int32_t* edge_row, int edge_mode, const float* sbf,
                           const float* w_sbf, const float* b_sbf, const int32_t* trip_rowptr,

@@ -831,6 +831,10 @@ int dispatch(Pass pass, AttnArgs a, int heads, int channels, int sbf_dim, hipStr
   if (channels % cpl) return X2G_EUNSUPPORTED;
   const int lph = channels / cpl;
   if (lph > 64 || (lph & (lph - 1))) return X2G_EUNSUPPORTED;
+  // the instantiations launch_cpl holds: a shape outside them is refused whatever E is (an empty batch
+  // used to return X2G_OK for it)
+  if (!(lph == 2 || lph == 4 || lph == 8 || (lph == 1 && cpl >= 4) || (lph == 16 && cpl == 1)))
+    return X2G_EUNSUPPORTED;
   a.D = D;
   a.H = heads;
   a.sqrt_c = static_cast<float>(sqrt(static_cast<double>(channels)));
