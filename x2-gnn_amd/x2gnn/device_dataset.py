@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .data import Batch
+from .padding import Capacity, solve_capacity
 
 _RING = 4  # pinned staging slots for the offset block: a slot is rewritten only after its copy has finished
 
@@ -238,6 +239,29 @@ class DeviceDataset:
         b = self.batch(idx[mine])
         b._store["_x2g_count_z"] = self._assemble(idx, atoms_only=True)[0]["x"]
         return b, len(mine), int(idx.shape[0])
+
+    # ------------------------------------------------------------------------------------------ fixed shape
+    def capacity(self, index_lists, fillers=1) -> Capacity:
+        """The one shape (:class:`x2gnn.padding.Capacity`) every batch of ``index_lists`` can be padded to by
+        ``fillers`` filler molecules (:func:`x2gnn.padding.filler_plan`), from the cached per-molecule sizes
+        (nothing touches the device).  Every list must have the same length; the molecules must all be symmetric
+        (the padded path is the molecular center-kernel path); ValueError otherwise, and where no shape within
+        the fillers' reach exists."""
+        from . import ops
+
+        lists = [self._indices(i) for i in index_lists]
+        if not lists or lists[0].shape[0] == 0:
+            raise ValueError("capacity needs at least one non-empty index list")
+        if any(i.shape[0] != lists[0].shape[0] for i in lists):
+            raise ValueError("every index list of a capacity must have the same length (drop or step the ragged "
+                             "last batch of an epoch on its own)")
+        pool = np.unique(np.concatenate(lists))
+        if not bool(self.symmetric[pool].all()):
+            raise ValueError("the padded path takes symmetric molecules only (every edge with its reverse, none twice)")
+        # (no filler molecule above ops.MOL_ROWPTR_MAX_ATOMS atoms, the per-molecule line-graph builder's bound)
+        return solve_capacity([self.nodes[i].sum() for i in lists], [self.edges[i].sum() for i in lists],
+                              [self.triplets[i].sum() for i in lists], int(self.max_degree[pool].max()), int(fillers),
+                              int(lists[0].shape[0]), int(self.nodes[pool].max()), ops.MOL_ROWPTR_MAX_ATOMS)
 
     # ------------------------------------------------------------------------------------------ one epoch
     def loader(self, batch_size, shuffle=True, seed=0, drop_last=False, indices=None):
