@@ -887,7 +887,8 @@ typedef struct {
 /* Data gradients of x2g_chain_fwd: dy (+ dy_add, may be NULL) = dL/d out_{n-1}; writes every
  * stage's dz (row-major where the stage's dz is set; T layout at dz_t + s * x2g_chain_t_floats when
  * dz_t is set), dx = dL/dx and d_res_ext = dL/d res_ext (NULL when no stage has RES_EXT).
- * Weight gradients: x2g_chain_wgrad over (in_t, dz_t), or x2g_wgrad_batched over row-major pairs. */
+ * Weight gradients: x2g_tiled_wgrad_flat jobs over the T planes or the row-major dz / inputs, or
+ * x2g_chain_wgrad over contiguous (in_t, dz_t). */
 int x2g_chain_bwd(const float* dy, const float* dy_add, const x2g_chain_bwd_stage* stages, int32_t n_stages,
                   int64_t rows, int32_t dim, float* dx, float* d_res_ext, float* dz_t, void* stream);
 /* x2g_chain_bwd for a chain run by x2g_chain_fwd_ln: also writes row_gstats[rows, 2] = (sum_c dx,
@@ -909,32 +910,17 @@ int x2g_chain_bwd_batch(const x2g_chain_bwd_job* jobs, int32_t num_jobs, int32_t
                         void* stream);
 
 /* Weight / bias gradients of every chain stage: dw[s] = dz_s^T in_s, db[s] = colsum(dz_s) (db[s] may
- * be NULL) from the T-layout operands of x2g_chain_fwd / x2g_chain_bwd; dw / db are host arrays of
- * n_stages device pointers.  Rows are split into fixed tile ranges per stage, the partials summed
- * in a fixed order; flags and slab layout as x2g_wgrad_batched (stage s's slabs at byte
- * s * (workspace / n_stages)). */
+ * be NULL) from the T-layout operands of x2g_chain_fwd / x2g_chain_bwd, stage s at
+ * + s * x2g_chain_t_floats(rows, dim); dw / db are host arrays of n_stages device pointers.  A wrapper:
+ * x2g_tiled_wgrad_flat (below) on n_stages layout-0 jobs, with its workspace size, its fixed
+ * summation order and its limits (dim = 128, rows * 512 B < 2^31, 16-byte aligned operands).  Flags
+ * X2G_ACCUM_WGRAD / X2G_DEFER_SLAB_SUM as x2g_linear_wgrad_ex; with X2G_DEFER_SLAB_SUM the partials
+ * stay in the workspace in the flat launch's slab layout and dw / db are not written: a caller that
+ * wants to sum them later calls x2g_tiled_wgrad_flat itself, which returns the slab jobs. */
 size_t x2g_chain_wgrad_workspace(int64_t rows, int32_t dim, int32_t n_stages);
 int x2g_chain_wgrad(const float* in_t, const float* dz_t, int32_t n_stages, int64_t rows, int32_t dim,
                     float* const* dw, float* const* db, int flags, void* workspace, size_t workspace_bytes,
                     void* stream);
-
-/* Weight / bias gradients of up to X2G_CHAIN_MAX_STAGES independent D x D Linear layers over the
- * same rows: dw_g = dy_g^T x_g, db_g = column sums of dy_g (db_g may be NULL).  Rows are split
- * into fixed chunks per layer (one workgroup each, f32 MFMA), chunk partials summed in a fixed
- * order (deterministic); flags X2G_ACCUM_WGRAD / X2G_DEFER_SLAB_SUM as x2g_linear_wgrad_ex.  Layer
- * g's slabs: x2g_wgrad_batched_splits() slabs of D*D floats starting at byte g * (workspace(rows,
- * dim, num_jobs) / num_jobs), then its bias slabs (D floats each). */
-typedef struct {
-  const float* dy; /* [rows, D] */
-  const float* x;  /* [rows, D] */
-  float* dw;       /* [D, D] */
-  float* db;       /* [D] or NULL */
-} x2g_wgrad_job;
-
-size_t x2g_wgrad_batched_workspace(int64_t rows, int32_t dim, int32_t num_jobs);
-int32_t x2g_wgrad_batched_splits(int64_t rows, int32_t dim, int32_t num_jobs);
-int x2g_wgrad_batched(const x2g_wgrad_job* jobs, int32_t num_jobs, int64_t rows, int32_t dim, int flags,
-                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- conv projections
  * The five projections SBFTransformerConv.forward applies to its node features
@@ -956,7 +942,7 @@ int x2g_conv_proj_fwd(const float* x, const float* rbf, int32_t rbf_dim, const f
 
 /* The gradients x2g_conv_proj_fwd's backward takes: grads[0..3] = dL/d(q, k, v, skip) with their
  * weights (w, or wt when given) and optional T-layout copies g_t for the weight gradient
- * (x2g_tiled_wgrad; all four NULL: the kernel instance without any copy code, for a weight gradient that
+ * (x2g_tiled_wgrad_flat; all four NULL: the kernel instance without any copy code, for a weight gradient that
  * reads g itself, X2G_TILED_DY_ROWMAJOR):  dx = dq Wq + dskip Ws (+ dx_add; dx may alias dx_add),  dxs = dk Wk + dv Wv
  * = dL/d x_src. */
 typedef struct {
@@ -978,9 +964,9 @@ int x2g_conv_proj_bwd_gate(const x2g_proj_grad* grads, int64_t rows, int32_t dim
                            int32_t rbf_dim, const float* w_rbf, float* dx, const float* dx_add, float* drbf,
                            float* dw_rbf, int flags, void* workspace, size_t workspace_bytes, void* stream);
 
-/* Weight / bias gradients of independent D x D Linear layers over the same rows from T-layout
- * operands: dw_j = dy_j^T x_j, db_j = colsum(dy_j) (db_j may be NULL); as x2g_chain_wgrad, with
- * each job's operands given separately (a T-layout tensor may serve several jobs). */
+/* Weight / bias gradients of independent D x D Linear layers from T-layout or row-major operands:
+ * dw_j = dy_j^T x_j, db_j = colsum(dy_j) (db_j may be NULL), each job's operands given separately
+ * (a tensor may serve several jobs). */
 typedef struct {
   const float* dy_t;
   const float* x_t;
@@ -988,20 +974,18 @@ typedef struct {
   float* db;
   int32_t ld;   /* 0: dw is a [D, D] weight; > 0: dw is the top-left of a D x D block of a larger */
   int32_t cols; /* weight with row stride ld, of which the first `cols` (<= D) columns are written */
-  /* Operand layouts (x2g_tiled_wgrad_flat / _flat_rows; x2g_tiled_wgrad takes 0 only).  0: both in the T
-   * layout.  X2G_TILED_DY_ROWMAJOR: dy_t points at a row-major [rows, D] tensor; X2G_TILED_X_ROWMAJOR:
-   * x_t does.  A row-major operand gives the same bits as its T-layout copy (rows past `rows` in the
-   * last tile count as zero, as the T layout's padding does).  Appended after `cols`, so callers that
-   * fill the first four or six fields keep today's meaning: x2g_abi_version() stays 17. */
+  /* Operand layouts.  0: both in the T layout.  X2G_TILED_DY_ROWMAJOR: dy_t points at a row-major
+   * [rows, D] tensor; X2G_TILED_X_ROWMAJOR: x_t does.  A row-major operand gives the same bits as its
+   * T-layout copy (rows past `rows` in the last tile count as zero, as the T layout's padding does). */
   int32_t layout;
   int32_t pad_;
 } x2g_tiled_job;
 #define X2G_TILED_DY_ROWMAJOR 1
 #define X2G_TILED_X_ROWMAJOR 2
 
-/* The same for up to X2G_TILED_MAX_JOBS jobs (e.g. every T-layout weight gradient of a backward)
- * in ONE launch: the jobs' 16-row tiles are concatenated and split evenly over one workgroup per
- * CU, so a job's partials are the few workgroups overlapping it (~256 + num_jobs slabs in all).
+/* Up to X2G_TILED_MAX_JOBS such jobs (e.g. every weight gradient of a backward) in ONE launch: the
+ * jobs' 16-row tiles are concatenated and split evenly over the workgroups (two per CU), so a job's
+ * partials are the few workgroups overlapping it (~512 + num_jobs slabs in all).
  * With X2G_DEFER_SLAB_SUM the num_jobs slab reductions are returned in slab_jobs (host array) for
  * the caller's x2g_slab_sum_batch; otherwise they are summed here. */
 #define X2G_TILED_MAX_JOBS 64
@@ -1015,10 +999,6 @@ size_t x2g_tiled_wgrad_flat_rows_workspace(const int64_t* job_rows, int32_t num_
 int x2g_tiled_wgrad_flat_rows(const x2g_tiled_job* jobs, const int64_t* job_rows, int32_t num_jobs, int32_t dim,
                               int flags, x2g_slab_job* slab_jobs, void* workspace, size_t workspace_bytes,
                               void* stream);
-
-size_t x2g_tiled_wgrad_workspace(int64_t rows, int32_t dim, int32_t num_jobs);
-int x2g_tiled_wgrad(const x2g_tiled_job* jobs, int32_t num_jobs, int64_t rows, int32_t dim, int flags,
-                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- small-table chains
  * X2-GNN's edge attribute is the embedding of the middle atom (xgnn.py:57-58), so the embedding
@@ -1076,7 +1056,7 @@ int x2g_feat_fwd(const float* x, const float* env, int64_t rows, int32_t in_dim,
                  void* stream);
 
 /* Data part of the backward: dz2_t = dy SiLU'(z2), dz1_t = (dz2 W2) SiLU'(z1), T layout (1 and 2
- * planes).  The weight gradients are x2g_tiled_wgrad jobs: dW1 block (o, i) = dz1_t plane o x
+ * planes).  The weight gradients are x2g_tiled_wgrad_flat jobs: dW1 block (o, i) = dz1_t plane o x
  * xs_t plane i (ld = in_dim, cols = min(128, in_dim - 128 i)), dW2 block i = dz2_t x y1_t plane i. */
 int x2g_feat_bwd(const float* dy, const float* z2_t, const float* z1_t, const float* w2, int64_t rows, float* dz2_t,
                  float* dz1_t, void* stream);

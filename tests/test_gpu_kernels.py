@@ -1310,9 +1310,10 @@ def _chain_ref(x, res, ws, bs, flags):
 @pytest.mark.parametrize("R", [21058, 1000, 37, 16, 1])
 @pytest.mark.parametrize("kind", ["trunk", "plain", "residual"])
 def test_row_chain_fwd_bwd_vs_torch(cuda, R, kind):
-    """x2g_chain_fwd / x2g_chain_bwd / x2g_wgrad_batched (ops.row_chain) against fp64 torch
-    autograd: the trunk tail of model.py:47-50 (7 stages), a plain Linear without activation,
-    and one ResidualLayer; ragged tiles (R % 16 != 0) and fewer rows than one tile."""
+    """x2g_chain_fwd / x2g_chain_bwd / x2g_tiled_wgrad_flat (ops.row_chain on plain parameters: stage 0's
+    weight gradient reads the row-major input) against fp64 torch autograd: the trunk tail of
+    model.py:47-50 (7 stages), a plain Linear without activation, and one ResidualLayer; ragged tiles
+    (R % 16 != 0) and fewer rows than one tile."""
     from x2gnn import ops
 
     S, H, RH, RE = ops.CHAIN_SILU, ops.CHAIN_HOLD, ops.CHAIN_RES_HELD, ops.CHAIN_RES_EXT

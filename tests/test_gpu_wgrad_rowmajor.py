@@ -9,7 +9,8 @@ owns exactly one tile.  R = 4001 (1255 tiles, 2-3 per workgroup), R = 10007 (313
 workgroup) and the row counts (20005, 9001, 1000, 37) (1880 tiles, 3-4 per workgroup) make workgroups
 run several steps of the double-buffered loop with both tiles of a step, tile offsets past 0 and
 multi-tile segments that end in a partial tile, and make some of them cross from a job of one layout
-into a job of another."""
+into a job of another.  x2g_chain_wgrad, the same launch over a chain's contiguous T planes, is checked at
+the ABI against it."""
 import ctypes
 
 import pytest
@@ -118,7 +119,7 @@ def test_tiled_wgrad_flat_rows_rowmajor_equals_t_layout(cuda, rows):
 
 
 def test_tiled_wgrad_refuses_unknown_layout_bits(cuda):
-    """An unknown layout bit is refused by the flat entry, any layout bit by x2g_tiled_wgrad; nothing runs."""
+    """An unknown layout bit is refused by the flat entry; nothing runs."""
     from x2gnn import _lib, ops
     from x2gnn._lib import ptr, stream_ptr
 
@@ -129,13 +130,71 @@ def test_tiled_wgrad_refuses_unknown_layout_bits(cuda):
     wsb = int(lib.x2g_tiled_wgrad_flat_workspace(16, 128, 1))
     ws = torch.empty(wsb, dtype=torch.uint8, device=cuda)
     assert lib.x2g_tiled_wgrad_flat(arr, 1, 16, 128, 0, None, ptr(ws), wsb, stream_ptr()) != 0
-    # x2g_tiled_wgrad (the launch per row count) takes T operands only
-    arr = (ops.TiledJob * 1)(ops.TiledJob(a.data_ptr(), a.data_ptr(), dw.data_ptr(), None, 0, 0, DY))
-    wsb = int(lib.x2g_tiled_wgrad_workspace(16, 128, 1))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=cuda)
-    assert lib.x2g_tiled_wgrad(arr, 1, 16, 128, 0, ptr(ws), wsb, stream_ptr()) != 0
     torch.cuda.synchronize()
     assert torch.equal(dw, torch.full_like(dw, 3.0))
+
+
+@pytest.mark.parametrize("n,nobias", [(1, None), (3, None), (3, 1)])
+@pytest.mark.parametrize("R", [1, 17, 37])
+def test_chain_wgrad_is_the_flat_launch_on_t_planes(cuda, R, n, nobias):
+    """x2g_chain_wgrad at the ABI: n stages over contiguous T planes (stage s at + s * x2g_chain_t_floats),
+    stage ``nobias`` with db[s] NULL; fewer rows than a tile, one tile plus a row, a ragged third tile.
+    dW / db within the weight-gradient bound of fp64 and the bits of x2g_tiled_wgrad_flat on the same
+    operands; X2G_ACCUM_WGRAD adds them to the destination's contents (one fp32 add of the summed slabs);
+    a workspace one byte short and X2G_DEFER_SLAB_SUM leave the destinations alone."""
+    from x2gnn import _lib, ops
+    from x2gnn._lib import ptr, stream_ptr
+
+    lib = _lib.load()
+    g = torch.Generator(device=cuda).manual_seed(100 * R + 10 * n + (nobias or 0))
+    dz = torch.randn(n, R, 128, device=cuda, generator=g)
+    x = torch.randn(n, R, 128, device=cuda, generator=g)
+    tf = int(lib.x2g_chain_t_floats(R, 128))
+    dz_t = torch.stack([_t_layout(dz[s]) for s in range(n)])
+    in_t = torch.stack([_t_layout(x[s]) for s in range(n)])
+    assert dz_t.shape == (n, tf)
+    wsb = int(lib.x2g_chain_wgrad_workspace(R, 128, n))
+    assert wsb == int(lib.x2g_tiled_wgrad_flat_workspace(R, 128, n)) > 0
+    ws = torch.empty(wsb, dtype=torch.uint8, device=cuda)
+
+    def fresh(fill):
+        dw = torch.full((n, 128, 128), fill, device=cuda)
+        db = torch.full((n, 128), fill, device=cuda)
+        return dw, db
+
+    def chain(dw, db, flags, ws_bytes):
+        dwa = (ctypes.c_void_p * n)(*[dw[s].data_ptr() for s in range(n)])
+        dba = (ctypes.c_void_p * n)(*[None if s == nobias else db[s].data_ptr() for s in range(n)])
+        rc = lib.x2g_chain_wgrad(ptr(in_t), ptr(dz_t), n, R, 128, dwa, dba, flags, ptr(ws), ws_bytes, stream_ptr())
+        torch.cuda.synchronize()
+        return rc
+
+    dw, db = fresh(0.0)
+    assert chain(dw, db, 0, wsb) == 0
+    for s in range(n):
+        ref = dz[s].double().t() @ x[s].double()
+        assert float((dw[s].double() - ref).abs().max()) <= 2e-5 * float(ref.abs().max()) + 1e-6, s
+        if s == nobias:
+            assert torch.equal(db[s], torch.zeros_like(db[s]))
+        else:
+            rb = dz[s].double().sum(0)
+            assert float((db[s].double() - rb).abs().max()) <= 2e-5 * float(rb.abs().max()) + 1e-6, s
+
+    fw, fb = fresh(0.0)
+    jobs = (ops.TiledJob * n)(*[ops.TiledJob(dz_t[s].data_ptr(), in_t[s].data_ptr(), fw[s].data_ptr(),
+                                             None if s == nobias else fb[s].data_ptr(), 0, 0, T) for s in range(n)])
+    assert lib.x2g_tiled_wgrad_flat(jobs, n, R, 128, 0, None, ptr(ws), wsb, stream_ptr()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(dw, fw) and torch.equal(db, fb)
+
+    aw, ab = fresh(3.0)
+    assert chain(aw, ab, ops.ACCUM_WGRAD, wsb) == 0
+    assert torch.equal(aw, 3.0 + dw) and torch.equal(ab, 3.0 + db)
+
+    for flags, ws_bytes, want in ((0, wsb - 1, 1003), (ops.DEFER_SLAB_SUM, wsb, 0)):
+        uw, ub = fresh(3.0)
+        assert chain(uw, ub, flags, ws_bytes) == want
+        assert torch.equal(uw, torch.full_like(uw, 3.0)) and torch.equal(ub, torch.full_like(ub, 3.0))
 
 
 def _record(monkeypatch):

@@ -22,7 +22,7 @@ def test_library_built_and_loads():
 
     assert os.path.exists(_lib.LIB_PATH), "run `make -C x2-gnn_amd` (or __graft_entry__.build())"
     lib = _lib.load()
-    assert lib.x2g_abi_version() == 17
+    assert lib.x2g_abi_version() == 18
 
 
 def test_every_declared_symbol_is_exported_and_bound():
@@ -80,6 +80,15 @@ def test_attention_rejects_uncompiled_shapes():
     assert rc == 1002
     rc = lib.x2g_sbf_attention_fwd(p, p, p, p, None, None, 0, p, p, p, p, p, 4, 0, 16, 8, 40, p, p, p, p, None)
     assert rc == 1002
+
+
+def test_chain_wgrad_refuses_rows_past_32bit_offsets():
+    """x2g_chain_wgrad addresses a job's rows with 32-bit byte offsets (rows * 512 B < 2^31): 2^22 rows are
+    refused with X2G_EUNSUPPORTED before any argument is read."""
+    from x2gnn import _lib
+
+    p = ctypes.c_void_p(16)  # never dereferenced: the size check fails first
+    assert _lib.load().x2g_chain_wgrad(p, p, 7, 1 << 22, 128, p, p, 0, p, 1 << 40, None) == 1002
 
 
 def test_center_backward_refuses_32bit_overflow_and_host_falls_back():

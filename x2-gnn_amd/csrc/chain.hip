@@ -922,206 +922,23 @@ __global__ void __launch_bounds__(kCThreads, 1) chain_bwd_v3_batch(const ChainBw
 }
 
 
-// ------------------------------------------------------------------------- batched weight gradients
-// dW_j[n][k] = sum_r dy_j[r][n] x_j[r][k] for up to 8 layers: workgroup (chunk, j) owns a fixed
-// range of rows of layer j; 32-row tiles of dy and x are staged through LDS (double-buffered,
-// next tile in registers during the MFMAs) and wave w accumulates dW rows 32w..32w+31 x all 128
-// columns (4 x v_mfma_f32_32x32x2_f32 accumulators) over the chunk; the chunk's partial goes to
-// its slab, summed later in a fixed order (x2g_slab_sum_batch).
-constexpr int kWThreads = 256;
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-struct WgradArgs {
-  x2g_wgrad_job job[X2G_CHAIN_MAX_STAGES];
-  float* part_w[X2G_CHAIN_MAX_STAGES];
-  float* part_b[X2G_CHAIN_MAX_STAGES];
-  int64_t R;
-  int chunk_rows;
-};
-
-__device__ __forceinline__ int wswz(int r, int c) { return r * 128 + 4 * ((c >> 2) ^ (r & 15)) + (c & 3); }
-
-__device__ __forceinline__ void wtile_load(const float* __restrict__ P, int64_t r0, int64_t r1, f4 (&v)[4]) {
-  const int tid = threadIdx.x, q = tid & 31;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int64_t r = r0 + (tid >> 5) + 8 * u;
-    const bool ok = r < r1;
-    const int64_t rc = ok ? r : r0;
-    v[u] = *reinterpret_cast<const f4*>(P + rc * kCD + 4 * q) * (ok ? 1.0f : 0.0f);
-  }
-}
-
-__device__ __forceinline__ void wtile_store(float* __restrict__ T, const f4 (&v)[4]) {
-  const int tid = threadIdx.x, q = tid & 31;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int r = (tid >> 5) + 8 * u;
-    *reinterpret_cast<f4*>(T + r * 128 + 4 * (q ^ (r & 15))) = v[u];
-  }
-}
-
-__global__ void __launch_bounds__(kWThreads, 2) wgrad_batched_kernel(const WgradArgs a) {
-  __shared__ __attribute__((aligned(16))) float Ds[2][32 * 128];
-  __shared__ __attribute__((aligned(16))) float Xs[2][32 * 128];
-  const int j = blockIdx.y;
-  const x2g_wgrad_job& J = a.job[j];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, i = lane & 31;
-  const int nb = 32 * wave;
-  const int64_t r0 = static_cast<int64_t>(blockIdx.x) * a.chunk_rows;
-  const int64_t r1 = r0 + a.chunk_rows < a.R ? r0 + a.chunk_rows : a.R;
-  floatx16 acc[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
-  float bsum = 0.f;
-  f4 vd[4], vx[4];
-  int buf = 0;
-  if (r0 < r1) {
-    wtile_load(J.dy, r0, r1, vd);
-    wtile_load(J.x, r0, r1, vx);
-  }
-  for (int64_t t = r0; t < r1; t += 32) {
-    wtile_store(Ds[buf], vd);
-    wtile_store(Xs[buf], vx);
-    __syncthreads();
-    if (t + 32 < r1) {  // the next tile's loads fly during the MFMAs
-      wtile_load(J.dy, t + 32, r1, vd);
-      wtile_load(J.x, t + 32, r1, vx);
-    }
-    const float* D = Ds[buf];
-    const float* X = Xs[buf];
-#pragma unroll
-    for (int sg = 0; sg < 2; ++sg) {
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        const int r = 16 * sg + s + 8 * h;
-        const float av = D[wswz(r, nb + i)];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, X[wswz(r, 32 * m + i)], acc[m], 0, 0, 0);
-      }
-    }
-    if (J.db && tid < 128) {
-#pragma unroll 8
-      for (int rr = 0; rr < 32; ++rr) bsum += D[wswz(rr, tid)];
-    }
-    buf ^= 1;  // the other buffer was last read before this tile's barrier
-  }
-  float* slab = a.part_w[j] + static_cast<int64_t>(blockIdx.x) * kCD * kCD;
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) slab[(nb + (e & 3) + 8 * (e >> 2) + 4 * h) * kCD + 32 * m + i] = acc[m][e];
-  if (J.db && tid < 128) a.part_b[j][static_cast<int64_t>(blockIdx.x) * kCD + tid] = bsum;
-}
-
-// ---------------------------------------------------------------- chain weight gradients (T layout)
-// dW_s = dz_s^T in_s over all rows: workgroup (c, s) owns a fixed range of 16-row tiles of stage s.
-// Two T tiles (32 rows) per step are copied into LDS as-is (8 KB each, double-buffered, the next
-// pair in registers during the MFMAs), so both MFMA operands come as ds_read_b128 of 4 consecutive
-// rows of one feature: wave w accumulates dW rows 16w..16w+15 x all 128 columns (8 blocks of
-// v_mfma_f32_16x16x4_f32).  Image position of (feature f, row quad q): f * 4 + (q ^ sigma(f)),
-// sigma(f) = 3 * ((f >> 3) & 1): conflict-free in every ds_read_b128 lane group.
-constexpr int kWTiles = 2;  // T tiles per step
+// ---------------------------------------------------------------- weight gradients of the row layers
+// dW = dz^T in over all rows, db = colsum(dz), for every 128 x 128 layer of a backward in one launch
+// (tiled_flat_kernel): a workgroup reduces a range of 16-row tiles of one job into a slab (dW rows
+// 16w + 4g + e, columns 16bk + rl).  Two tiles (32 rows) of each operand per step are copied into LDS
+// as-is (8 KB each) by buffer_load ... lds (no registers: each wave's instruction lands 1 KB
+// lane-linearly, the swizzle applied to the source addresses), so both MFMA operands of a T tile come
+// as ds_read_b128 of 4 consecutive rows of one feature: wave w accumulates dW rows 16w..16w+15 x all
+// 128 columns (8 blocks of v_mfma_f32_16x16x4_f32).  T image position of (feature f, row quad q):
+// f * 4 + (q ^ sigma(f)), sigma(f) = 3 * ((f >> 3) & 1): conflict-free in every ds_read_b128 lane group.
+constexpr int kWTiles = 2;   // tiles per step
+constexpr int kFlatWPC = 2;  // 512-thread workgroups per CU (66 KB of LDS each: 4 waves per SIMD)
 
 __device__ __forceinline__ int tpos(int f, int q) { return f * 4 + (q ^ (((f >> 3) & 1) * 3)); }
 
-struct ChainWgradArgs {
-  const float* in_t[X2G_CHAIN_MAX_STAGES];  // per job: the layer input and dz, T layout
-  const float* dz_t[X2G_CHAIN_MAX_STAGES];
-  int64_t ntiles;
-  float* part_w[X2G_CHAIN_MAX_STAGES];
-  float* part_b[X2G_CHAIN_MAX_STAGES];
-  int has_b[X2G_CHAIN_MAX_STAGES];
-  int splits;
-};
-
-// Three LDS buffers, filled by global_load_lds (no registers: each wave's instruction lands 1 KB
-// lane-linearly, the swizzle applied to the source addresses), two steps in flight ahead of the
-// product; raw s_barrier with counted vmcnt waits so the in-flight copies survive the barriers.
-// One call reduces tiles [t0, t1) of one job into a slab (dW rows 16w + 4g + e, columns 16bk + rl).
-template <int NB, bool SPREAD = true, int WT = kWTiles>  // NB LDS buffers: NB - 1 steps in flight ahead of the product;
-// SPREAD: the bias column sums over all eight waves (else waves 0-1 only)
-__device__ __forceinline__ void tiled_segment(const float* __restrict__ dz, const float* __restrict__ xin, int64_t t0,
-                                              int64_t t1, bool has_b, float* __restrict__ slab,
-                                              float* __restrict__ slab_b, f4 (*Ds)[WT][512],
-                                              f4 (*Xs)[WT][512]) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int rl = lane & 15, g = lane >> 4;
-  const int nsteps = static_cast<int>((t1 - t0 + WT - 1) / WT);
-  // LDS position P = 64w + lane of a tile image holds source chunk (P >> 2) * 4 + ((P & 3) ^ sigma)
-  const int P = 64 * w + lane;
-  const int src_chunk = (P >> 2) * 4 + ((P & 3) ^ (((P >> 5) & 1) * 3));
-  auto issue = [&](int step) {  // the step's tiles into buffer step % NB (tiles past t1: tile t0)
-    const int b = step % NB;
-#pragma unroll
-    for (int k = 0; k < WT; ++k) {
-      int64_t t = t0 + static_cast<int64_t>(step) * WT + k;
-      t = t < t1 ? t : t0;
-      __builtin_amdgcn_global_load_lds(dz + t * 2048 + 4 * src_chunk, &Ds[b][k][64 * w], 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(xin + t * 2048 + 4 * src_chunk, &Xs[b][k][64 * w], 16, 0, 0);
-    }
-  };
-  f4 acc[8];
-#pragma unroll
-  for (int bk = 0; bk < 8; ++bk) acc[bk] = zero4();
-  float bsum = 0.f;
-#pragma unroll
-  for (int p = 0; p < NB - 1; ++p)
-    if (p < nsteps) issue(p);
-  for (int i = 0; i < nsteps; ++i) {
-    // this step's copies are done when at most the later issued steps' 2 * WT each remain
-    const int ahead = nsteps - 1 - i < NB - 2 ? nsteps - 1 - i : NB - 2;
-    if (ahead >= 2)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * WT) : "memory");
-    else if (ahead == 1)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * WT) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // every wave's copies of this step have landed; step i-1 is read
-    if (i + NB - 1 < nsteps) issue(i + NB - 1);
-    const int b = i % NB;
-#pragma unroll
-    for (int k = 0; k < WT; ++k) {
-      if (t0 + static_cast<int64_t>(i) * WT + k >= t1) break;  // wave-uniform
-      const f4 av = Ds[b][k][tpos(16 * w + rl, g)];
-      f4 bv[8];
-#pragma unroll
-      for (int bk = 0; bk < 8; ++bk) bv[bk] = Xs[b][k][tpos(16 * bk + rl, g)];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int bk = 0; bk < 8; ++bk) acc[bk] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[bk][e], acc[bk], 0, 0, 0);
-      if (SPREAD && has_b) {  // bias: thread (q, f) sums feature f's row quad q (every wave takes a share)
-        const f4 v = Ds[b][k][tpos(tid & (kCD - 1), tid >> 7)];
-        bsum += (v[0] + v[1]) + (v[2] + v[3]);
-      }
-      if (!SPREAD && tid < 128) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f4 v = Ds[b][k][tpos(tid, q)];
-          bsum += (v[0] + v[1]) + (v[2] + v[3]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int bk = 0; bk < 8; ++bk)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) slab[(16 * w + 4 * g + e) * kCD + 16 * bk + rl] = acc[bk][e];
-  if (!SPREAD && has_b && tid < 128) slab_b[tid] = bsum;
-  if (SPREAD && has_b) {  // the four row-quad partials of each feature, in quad order
-    __shared__ float bred[4 * kCD];
-    bred[tid] = bsum;
-    __syncthreads();
-    if (tid < kCD) slab_b[tid] = ((bred[tid] + bred[kCD + tid]) + bred[2 * kCD + tid]) + bred[3 * kCD + tid];
-  }
-}
-
-// NB = 2 with the two buffers as distinct NAMED LDS arrays and the step loop unrolled by two, so every
-// buffer index is static.  With one dynamically indexed [NB] array the compiler could not tell the
+// Two LDS buffers, step i + 1's copy in flight under step i's MFMAs; raw s_barrier so the in-flight
+// copy survives it.  The two buffers are distinct NAMED LDS arrays and the step loop is unrolled by
+// two, so every buffer index is static.  With one dynamically indexed array the compiler could not tell the
 // buffer a step reads from the one the next step's copies are filling, and waited for those copies
 // (vmcnt(0)) before the step's first LDS read: step i + 1's copy never ran under step i's MFMAs.  The
 // next step's copy is issued unconditionally (past the segment's end it re-reads tile t0 into the idle
@@ -1137,11 +954,13 @@ __device__ __forceinline__ void tiled_segment(const float* __restrict__ dz, cons
 // descriptor's range and land as zeros.
 __device__ __forceinline__ int rpos(int r, int f) { return 128 * r + 4 * ((f >> 2) ^ (r & 12)) + (f & 3); }
 
-template <bool SPREAD, int WT, bool DR, bool XR>
-__device__ __forceinline__ void tiled_segment2(const float* __restrict__ dz, const float* __restrict__ xin, int64_t t0,
-                                               int64_t t1, int64_t rows, bool has_b, float* __restrict__ slab,
-                                               float* __restrict__ slab_b, f4 (*D0)[512], f4 (*X0)[512],
-                                               f4 (*D1)[512], f4 (*X1)[512], float* __restrict__ bred) {
+// One call reduces tiles [t0, t1) of one job into a slab.
+template <bool DR, bool XR>
+__device__ __forceinline__ void flat_segment(const float* __restrict__ dz, const float* __restrict__ xin, int64_t t0,
+                                             int64_t t1, int64_t rows, bool has_b, float* __restrict__ slab,
+                                             float* __restrict__ slab_b, f4 (*D0)[512], f4 (*X0)[512],
+                                             f4 (*D1)[512], f4 (*X1)[512], float* __restrict__ bred) {
+  constexpr int WT = kWTiles;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int rl = lane & 15, g = lane >> 4;
   const int nsteps = static_cast<int>((t1 - t0 + WT - 1) / WT);
@@ -1215,16 +1034,9 @@ __device__ __forceinline__ void tiled_segment2(const float* __restrict__ dz, con
       for (int e = 0; e < 4; ++e)
 #pragma unroll
         for (int bk = 0; bk < 8; ++bk) acc[bk] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[bk][e], acc[bk], 0, 0, 0);
-      if (SPREAD && has_b) {
+      if (has_b) {  // bias: thread (q, f) sums feature f's row quad q (every wave takes a share)
         const f4 v = quad(Dc[k], DR, tid & (kCD - 1), tid >> 7);
         bsum += (v[0] + v[1]) + (v[2] + v[3]);
-      }
-      if (!SPREAD && tid < 128) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f4 v = quad(Dc[k], DR, tid, q);
-          bsum += (v[0] + v[1]) + (v[2] + v[3]);
-        }
       }
     }
   };
@@ -1239,29 +1051,17 @@ __device__ __forceinline__ void tiled_segment2(const float* __restrict__ dz, con
   for (int bk = 0; bk < 8; ++bk)
 #pragma unroll
     for (int e = 0; e < 4; ++e) slab[(16 * w + 4 * g + e) * kCD + 16 * bk + rl] = acc[bk][e];
-  if (!SPREAD && has_b && tid < 128) slab_b[tid] = bsum;
-  if (SPREAD && has_b) {  // the four row-quad partials of each feature, in quad order
+  if (has_b) {  // the four row-quad partials of each feature, in quad order
     bred[tid] = bsum;
     __syncthreads();
     if (tid < kCD) slab_b[tid] = ((bred[tid] + bred[kCD + tid]) + bred[2 * kCD + tid]) + bred[3 * kCD + tid];
   }
 }
 
-__global__ void __launch_bounds__(kCThreads, 1) chain_wgrad_kernel(const ChainWgradArgs a) {
-  __shared__ f4 Ds[3][kWTiles][512];
-  __shared__ f4 Xs[3][kWTiles][512];
-  const int s = blockIdx.y, c = blockIdx.x;
-  const int64_t t0 = c * a.ntiles / a.splits, t1 = (c + 1) * a.ntiles / a.splits;
-  tiled_segment<3>(a.dz_t[s], a.in_t[s], t0, t1, a.has_b[s] != 0, a.part_w[s] + static_cast<int64_t>(c) * kCD * kCD,
-                a.part_b[s] + static_cast<int64_t>(c) * kCD, Ds, Xs);
-}
-
-// Every T-layout weight gradient of a backward in ONE launch: the jobs' tiles are concatenated
-// (job j owns [tile0[j], tile0[j + 1]): jobs may differ in row count) and workgroup i takes the equal share
-// [i * total / G, (i + 1) * total / G), i.e. at most a few job segments; each segment leaves one
-// slab, job j's slabs contiguous from workgroup wg_lo[j] on.  Versus one launch per layer with
-// 256 / jobs splits per job: the same MFMA work, ~256 + jobs slabs in all instead of 256 per
-// launch, and one launch tail.
+// The jobs' tiles are concatenated (job j owns [tile0[j], tile0[j + 1]): jobs may differ in row count)
+// and workgroup i takes the equal share [i * total / G, (i + 1) * total / G), i.e. at most a few job
+// segments; each segment leaves one slab, job j's slabs contiguous from workgroup wg_lo[j] on: ~G + jobs
+// slabs in all and one launch tail.
 struct TiledFlatArgs {
   const float* in_t[X2G_TILED_MAX_JOBS];
   const float* dz_t[X2G_TILED_MAX_JOBS];
@@ -1276,14 +1076,11 @@ struct TiledFlatArgs {
   int njobs;
 };
 
-// NB LDS buffers of 2 x WT tiles (NB x WT x 16 KB; NB - 1 steps in flight); WPC workgroups per CU
-template <int NB, bool SPREAD = true, int WT = kWTiles, int WPC = 1>
-__global__ void __launch_bounds__(kCThreads, 2 * WPC) tiled_flat_kernel(const TiledFlatArgs a) {
-  static_assert(NB == 2, "the flat launch's two named buffers (tiled_segment2)");
-  __shared__ f4 D0[WT][512];
-  __shared__ f4 X0[WT][512];
-  __shared__ f4 D1[WT][512];
-  __shared__ f4 X1[WT][512];
+__global__ void __launch_bounds__(kCThreads, 2 * kFlatWPC) tiled_flat_kernel(const TiledFlatArgs a) {
+  __shared__ f4 D0[kWTiles][512];
+  __shared__ f4 X0[kWTiles][512];
+  __shared__ f4 D1[kWTiles][512];
+  __shared__ f4 X1[kWTiles][512];
   __shared__ float bred[4 * kCD];  // the bias row-quad partials
   const int64_t G = gridDim.x, i = blockIdx.x;
   const int64_t lo = i * a.total / G, hi = (i + 1) * a.total / G;
@@ -1295,9 +1092,9 @@ __global__ void __launch_bounds__(kCThreads, 2 * WPC) tiled_flat_kernel(const Ti
     if (s0 >= s1) continue;
     __syncthreads();  // a previous segment's last buffers are no longer read
     const int64_t k = i - a.wg_lo[j];
-    // one instance of the step loop per operand layout pair (workgroup-uniform; T / T is the one before)
+    // one instance of the step loop per operand layout pair (workgroup-uniform)
     auto seg = [&](auto dr, auto xr) {
-      tiled_segment2<SPREAD, WT, decltype(dr)::value, decltype(xr)::value>(
+      flat_segment<decltype(dr)::value, decltype(xr)::value>(
           a.dz_t[j], a.in_t[j], s0 - a.tile0[j], s1 - a.tile0[j], a.rows[j], a.has_b[j] != 0,
           a.slab_w[j] + k * kCD * kCD, a.slab_b[j] + k * kCD, D0, X0, D1, X1, bred);
     };
@@ -1310,15 +1107,6 @@ __global__ void __launch_bounds__(kCThreads, 2 * WPC) tiled_flat_kernel(const Ti
       default: seg(R_{}, R_{}); break;
     }
   }
-}
-
-inline int chain_wgrad_splits_of(int64_t ntiles, int stages) {
-  // at most one workgroup per CU over all stages (96 KB of LDS each: a 257th would run alone in a
-  // second round), >= 4 tiles each
-  int64_t per = 256 / stages;
-  const int64_t cap = (ntiles + 3) / 4;
-  if (per > cap) per = cap;
-  return static_cast<int>(per < 1 ? 1 : per);
 }
 
 // ---------------------------------------------------------------- conv projections
@@ -1654,15 +1442,6 @@ __global__ void __launch_bounds__(kCThreads, 2) conv_proj_bwd_gate_kernel(const 
 
 inline bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
-// rows per weight-gradient chunk: about two workgroups per CU over all jobs, >= 64 rows
-inline int wgrad_chunk_rows(int64_t R, int jobs) {
-  const int64_t target = 512;
-  const int64_t per_job = (target + jobs - 1) / jobs;
-  int64_t cr = (R + per_job - 1) / per_job;
-  cr = (cr + 31) / 32 * 32;
-  return static_cast<int>(cr < 64 ? 64 : cr);
-}
-
 }  // namespace
 }  // namespace x2g
 
@@ -1879,93 +1658,6 @@ X2G_API int x2g_chain_bwd_batch(const x2g_chain_bwd_job* jobs, int32_t n_jobs, i
   return last_launch_status();
 }
 
-X2G_API int32_t x2g_wgrad_batched_splits(int64_t rows, int32_t dim, int32_t num_jobs) {
-  if (rows <= 0 || dim != kCD || num_jobs < 1 || num_jobs > X2G_CHAIN_MAX_STAGES) return 0;
-  const int cr = wgrad_chunk_rows(rows, num_jobs);
-  return static_cast<int32_t>((rows + cr - 1) / cr);
-}
-
-X2G_API size_t x2g_wgrad_batched_workspace(int64_t rows, int32_t dim, int32_t num_jobs) {
-  const int32_t splits = x2g_wgrad_batched_splits(rows, dim, num_jobs);
-  return static_cast<size_t>(num_jobs > 0 ? num_jobs : 0) * splits * (kCD * kCD + kCD) * sizeof(float);
-}
-
-X2G_API int x2g_wgrad_batched(const x2g_wgrad_job* jobs, int32_t num_jobs, int64_t rows, int32_t dim, int flags,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-  if (!jobs || num_jobs < 1 || num_jobs > X2G_CHAIN_MAX_STAGES || rows <= 0 || dim <= 0 ||
-      (flags & ~(X2G_ACCUM_WGRAD | X2G_DEFER_SLAB_SUM)))
-    return X2G_EINVAL;
-  if (dim != kCD || rows * kCD * 4 >= (int64_t(1) << 31)) return X2G_EUNSUPPORTED;
-  const size_t need = x2g_wgrad_batched_workspace(rows, dim, num_jobs);
-  if (!workspace || workspace_bytes < need) return X2G_EWORKSPACE;
-  WgradArgs a{};
-  a.R = rows;
-  a.chunk_rows = wgrad_chunk_rows(rows, num_jobs);
-  const int splits = x2g_wgrad_batched_splits(rows, dim, num_jobs);
-  const size_t per_job = need / num_jobs;
-  x2g_slab_job sj[X2G_CHAIN_MAX_STAGES];
-  for (int j = 0; j < num_jobs; ++j) {
-    const x2g_wgrad_job& J = jobs[j];
-    if (!J.dy || !J.x || !J.dw) return X2G_EINVAL;
-    if (!al16(J.dy) || !al16(J.x)) return X2G_EUNSUPPORTED;
-    a.job[j] = J;
-    a.part_w[j] = reinterpret_cast<float*>(static_cast<char*>(workspace) + per_job * j);
-    a.part_b[j] = a.part_w[j] + static_cast<int64_t>(splits) * kCD * kCD;
-    sj[j] = x2g_slab_job{a.part_w[j], J.db ? a.part_b[j] : nullptr, J.dw, J.db, kCD * kCD, J.db ? kCD : 0, splits};
-  }
-  hipStream_t st = as_stream(stream);
-  wgrad_batched_kernel<<<dim3(static_cast<unsigned>(splits), static_cast<unsigned>(num_jobs)), kWThreads, 0, st>>>(a);
-  const int rc = last_launch_status();
-  if (rc || (flags & X2G_DEFER_SLAB_SUM)) return rc;
-  return x2g_slab_sum_batch(sj, num_jobs, (flags & X2G_ACCUM_WGRAD) ? 1 : 0, stream);
-}
-
-static int32_t chain_wgrad_splits(int64_t rows, int32_t dim, int32_t n_stages) {
-  if (rows <= 0 || dim != kCD || n_stages < 1 || n_stages > X2G_CHAIN_MAX_STAGES) return 0;
-  return chain_wgrad_splits_of((rows + 15) / 16, n_stages);
-}
-
-X2G_API size_t x2g_chain_wgrad_workspace(int64_t rows, int32_t dim, int32_t n_stages) {
-  const int32_t splits = chain_wgrad_splits(rows, dim, n_stages);
-  return static_cast<size_t>(splits > 0 ? n_stages : 0) * splits * (kCD * kCD + kCD) * sizeof(float);
-}
-
-X2G_API int x2g_chain_wgrad(const float* in_t, const float* dz_t, int32_t n_stages, int64_t rows, int32_t dim,
-                            float* const* dw, float* const* db, int flags, void* workspace, size_t workspace_bytes,
-                            void* stream) {
-  if (!in_t || !dz_t || !dw || n_stages < 1 || n_stages > X2G_CHAIN_MAX_STAGES || rows <= 0 || dim <= 0 ||
-      (flags & ~(X2G_ACCUM_WGRAD | X2G_DEFER_SLAB_SUM)))
-    return X2G_EINVAL;
-  if (dim != kCD || rows * kCD * 4 >= (int64_t(1) << 31)) return X2G_EUNSUPPORTED;
-  if (!al16(in_t) || !al16(dz_t)) return X2G_EUNSUPPORTED;
-  const size_t need = x2g_chain_wgrad_workspace(rows, dim, n_stages);
-  if (!workspace || workspace_bytes < need) return X2G_EWORKSPACE;
-  ChainWgradArgs a{};
-  const int64_t tf = x2g_chain_t_floats(rows, dim);
-  for (int j = 0; j < n_stages; ++j) {
-    a.in_t[j] = in_t + j * tf;
-    a.dz_t[j] = dz_t + j * tf;
-  }
-  a.ntiles = (rows + 15) / 16;
-  a.splits = chain_wgrad_splits(rows, dim, n_stages);
-  const size_t per = need / n_stages;
-  x2g_slab_job sj[X2G_CHAIN_MAX_STAGES];
-  for (int j = 0; j < n_stages; ++j) {
-    if (!dw[j]) return X2G_EINVAL;
-    const bool hb = db && db[j];
-    a.part_w[j] = reinterpret_cast<float*>(static_cast<char*>(workspace) + per * j);
-    a.part_b[j] = a.part_w[j] + static_cast<int64_t>(a.splits) * kCD * kCD;
-    a.has_b[j] = hb;
-    sj[j] = x2g_slab_job{a.part_w[j], hb ? a.part_b[j] : nullptr, dw[j], hb ? db[j] : nullptr, kCD * kCD,
-                         hb ? kCD : 0, a.splits};
-  }
-  chain_wgrad_kernel<<<dim3(static_cast<unsigned>(a.splits), static_cast<unsigned>(n_stages)), kCThreads, 0,
-                       as_stream(stream)>>>(a);
-  const int rc = last_launch_status();
-  if (rc || (flags & X2G_DEFER_SLAB_SUM)) return rc;
-  return x2g_slab_sum_batch(sj, n_stages, (flags & X2G_ACCUM_WGRAD) ? 1 : 0, stream);
-}
-
 static inline unsigned v2_grid(int64_t rows) {
   const int64_t nblk = (rows + 15) / 16;
   return static_cast<unsigned>(nblk < 256 ? nblk : 256);
@@ -2076,9 +1768,7 @@ X2G_API int x2g_conv_proj_bwd_gate(const x2g_proj_grad* grads, int64_t rows, int
   return x2g_slab_sum_batch(&sj, 1, (flags & X2G_ACCUM_WGRAD) ? 1 : 0, stream);
 }
 
-// ---- one launch for many jobs (x2g_tiled_wgrad_flat)
-// two 512-thread workgroups per CU (66 KB of LDS and 100 VGPRs each: 4 waves per SIMD)
-constexpr int kFlatWPC = 2;
+// ---- the row layers' weight gradients (x2g_tiled_wgrad_flat, x2g_chain_wgrad)
 static inline unsigned flat_grid(int64_t total) {
   const int64_t cap = 256 * kFlatWPC;
   return static_cast<unsigned>(total < cap ? (total < 1 ? 1 : total) : cap);
@@ -2164,7 +1854,7 @@ static int flat_launch(const x2g_tiled_job* jobs, const int64_t* rows, int32_t n
   // barriers run under the other's MFMAs (+1.4 % in the step A/B over one workgroup per CU with two
   // 4-tile buffers, which was +0.7 % over r2's one workgroup with four 2-tile buffers; three 3-tile
   // buffers: -0.3 %).  Twice the slabs (512 + jobs), summed by the deferred slab pass.
-  tiled_flat_kernel<2, true, 2, kFlatWPC><<<static_cast<unsigned>(G), kCThreads, 0, as_stream(stream)>>>(a);
+  tiled_flat_kernel<<<static_cast<unsigned>(G), kCThreads, 0, as_stream(stream)>>>(a);
   const int rc = last_launch_status();
   if (rc) return rc;
   if (flags & X2G_DEFER_SLAB_SUM) {
@@ -2199,40 +1889,29 @@ X2G_API int x2g_tiled_wgrad_flat_rows(const x2g_tiled_job* jobs, const int64_t* 
   return flat_launch(jobs, job_rows, num_jobs, dim, flags, slab_jobs, workspace, workspace_bytes, stream);
 }
 
-X2G_API size_t x2g_tiled_wgrad_workspace(int64_t rows, int32_t dim, int32_t num_jobs) {
-  return x2g_chain_wgrad_workspace(rows, dim, num_jobs);
+// a chain's stages as n_stages layout-0 jobs of the flat launch over the contiguous T planes
+X2G_API size_t x2g_chain_wgrad_workspace(int64_t rows, int32_t dim, int32_t n_stages) {
+  if (n_stages > X2G_CHAIN_MAX_STAGES) return 0;
+  return x2g_tiled_wgrad_flat_workspace(rows, dim, n_stages);
 }
 
-X2G_API int x2g_tiled_wgrad(const x2g_tiled_job* jobs, int32_t num_jobs, int64_t rows, int32_t dim, int flags,
-                            void* workspace, size_t workspace_bytes, void* stream) {
-  if (!jobs || num_jobs < 1 || num_jobs > X2G_CHAIN_MAX_STAGES || rows <= 0 || dim <= 0 ||
+X2G_API int x2g_chain_wgrad(const float* in_t, const float* dz_t, int32_t n_stages, int64_t rows, int32_t dim,
+                            float* const* dw, float* const* db, int flags, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  if (!in_t || !dz_t || !dw || n_stages < 1 || n_stages > X2G_CHAIN_MAX_STAGES || rows <= 0 || dim <= 0 ||
       (flags & ~(X2G_ACCUM_WGRAD | X2G_DEFER_SLAB_SUM)))
     return X2G_EINVAL;
+  // (before dw / db are read; the row limit is flat_tiles()')
   if (dim != kCD || rows * kCD * 4 >= (int64_t(1) << 31)) return X2G_EUNSUPPORTED;
-  const size_t need = x2g_tiled_wgrad_workspace(rows, dim, num_jobs);
-  if (!workspace || workspace_bytes < need) return X2G_EWORKSPACE;
-  ChainWgradArgs a{};
-  a.ntiles = (rows + 15) / 16;
-  a.splits = chain_wgrad_splits(rows, dim, num_jobs);
-  const size_t per = need / num_jobs;
-  x2g_slab_job sj[X2G_CHAIN_MAX_STAGES];
-  for (int j = 0; j < num_jobs; ++j) {
-    const x2g_tiled_job& J = jobs[j];
-    if (!J.dy_t || !J.x_t || !J.dw) return X2G_EINVAL;
-    if (!al16(J.dy_t) || !al16(J.x_t)) return X2G_EUNSUPPORTED;
-    if (J.layout) return X2G_EUNSUPPORTED;  // row-major operands: the flat launch only
-    a.in_t[j] = J.x_t;
-    a.dz_t[j] = J.dy_t;
-    a.part_w[j] = reinterpret_cast<float*>(static_cast<char*>(workspace) + per * j);
-    a.part_b[j] = a.part_w[j] + static_cast<int64_t>(a.splits) * kCD * kCD;
-    a.has_b[j] = J.db != nullptr;
-    if (J.ld < 0 || (J.ld > 0 && (J.cols < 1 || J.cols > kCD || J.cols > J.ld))) return X2G_EINVAL;
-    sj[j] = x2g_slab_job{a.part_w[j], J.db ? a.part_b[j] : nullptr, J.dw, J.db, kCD * kCD, J.db ? kCD : 0,
-                         a.splits, J.ld, J.cols};
+  if (!al16(in_t) || !al16(dz_t)) return X2G_EUNSUPPORTED;
+  const int64_t tf = x2g_chain_t_floats(rows, dim);
+  x2g_tiled_job jobs[X2G_CHAIN_MAX_STAGES] = {};
+  for (int s = 0; s < n_stages; ++s) {
+    jobs[s].dy_t = dz_t + s * tf;
+    jobs[s].x_t = in_t + s * tf;
+    jobs[s].dw = dw[s];
+    jobs[s].db = db ? db[s] : nullptr;
   }
-  chain_wgrad_kernel<<<dim3(static_cast<unsigned>(a.splits), static_cast<unsigned>(num_jobs)), kCThreads, 0,
-                       as_stream(stream)>>>(a);
-  const int rc = last_launch_status();
-  if (rc || (flags & X2G_DEFER_SLAB_SUM)) return rc;
-  return x2g_slab_sum_batch(sj, num_jobs, (flags & X2G_ACCUM_WGRAD) ? 1 : 0, stream);
+  x2g_slab_job sj[X2G_CHAIN_MAX_STAGES];  // X2G_DEFER_SLAB_SUM: dropped, the partials stay in the workspace
+  return x2g_tiled_wgrad_flat(jobs, n_stages, rows, dim, flags, sj, workspace, workspace_bytes, stream);
 }

@@ -13,7 +13,7 @@
 //              128-feature planes): x*env, z1, SiLU(z1), z2.
 //   backward — ONE data kernel (dz2 = dy SiLU'(z2), dy1 = dz2 W2, dz1 = dy1 SiLU'(z1), both dz in
 //              T layout) and the weight gradients as eight 128 x 128 T-layout jobs of
-//              x2g_tiled_wgrad (mat_trans: 2 x 3 blocks, emb_trans: 1 x 2), written into the
+//              x2g_tiled_wgrad_flat (mat_trans: 2 x 3 blocks, emb_trans: 1 x 2), written into the
 //              weights through strided slab sums.
 //
 // MFMA operand convention as the row chains: lane l = (i = l & 15, g = l >> 4); the contraction

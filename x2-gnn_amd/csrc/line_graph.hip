@@ -629,7 +629,7 @@ X2G_API int x2g_batch_meta(const int64_t* edge_index, const int64_t* x, const in
   return last_launch_status();
 }
 
-X2G_API int x2g_abi_version(void) { return 17; }
+X2G_API int x2g_abi_version(void) { return 18; }
 
 X2G_API const char* x2g_status_string(int status) {
   switch (status) {
@@ -912,7 +912,9 @@ __global__ void __launch_bounds__(64) center_pack_window_kernel(const int32_t* _
   const int lane = threadIdx.x;
   const int a0 = kSchedWin * static_cast<int>(blockIdx.x);
   const int na = static_cast<int>(N - a0 < kSchedWin ? N - a0 : kSchedWin);
-  const int d = lane < na ? rowptr[a0 + lane + 1] - rowptr[a0 + lane] : -1;
+  // (a row pointer that is not monotone, as x2g_batch_meta leaves for an unsorted edge list, must not index
+  // the bins below zero: its negative degrees count as 0 here and in center_sched_place_kernel)
+  const int d = lane < na ? max(rowptr[a0 + lane + 1] - rowptr[a0 + lane], 0) : -1;
   if (lane < na) atomicAdd(&ws.hist[min(d, kSchedDeg)], 1);
   int rank = 0;  // by decreasing degree, ties by index
   for (int k = 0; k < na; ++k) {
@@ -1022,7 +1024,7 @@ __global__ void __launch_bounds__(64) center_sched_place_kernel(const int32_t* _
   const int64_t s = a0 + lane;
   int d = 0;
   if (lane < na) {
-    d = min(rowptr[s + 1] - rowptr[s], kSchedDeg);
+    d = min(max(rowptr[s + 1] - rowptr[s], 0), kSchedDeg);
     center_order[ws.apre[d] + atomicAdd(&ws.acur[d], 1)] = static_cast<int32_t>(s);
     const int tu = ws.t_unit[s];
     if (tu >= 0) {  // lane u < nu: unit u of the window

@@ -140,6 +140,9 @@ def _meta_on_device(data):
     call("x2g_batch_meta", ptr(ei), ptr(x), ptr(batch), E, n, B, ptr(src), ptr(dst), ptr(src_t), ptr(dst_t),
          ptr(atom_t), ptr(line_ptr), ptr(mol_ptr), ptr(rowptr), ptr(info), stream_ptr())
     host = info.cpu().numpy()  # the one device->host copy: sizes per molecule and the flags
+    if host[3 * B + 4]:  # (before anything is launched over the row pointer of such a list: it is not monotone)
+        raise ValueError("edge_index must list each directed edge once, sorted by (source, destination) "
+                         "(the order the reference's radius graph emits, atom_graph.py:42-45)")
     # the center-atom kernels' schedule (degree order, the fused forward's packs and atom_info), made on the device
     # as collate makes it on the host for x2gnn's own batches (data.center_packs); enqueued after the read-back,
     # which then waits for nothing it does not need
@@ -147,9 +150,6 @@ def _meta_on_device(data):
 
     c_order, p_order, p_ptr, a_info = center_schedule(rowptr, src_t, n)
     mp_, lp, tr, fl = host[:B + 1], host[B + 1:2 * B + 2], host[2 * B + 2:3 * B + 2], host[3 * B + 2:]
-    if fl[2]:
-        raise ValueError("edge_index must list each directed edge once, sorted by (source, destination) "
-                         "(the order the reference's radius graph emits, atom_graph.py:42-45)")
     index = {"_x2g_edge_src": src, "_x2g_edge_dst": dst, "_x2g_src_type": src_t, "_x2g_dst_type": dst_t,
              "_x2g_atom_type": atom_t, "_x2g_line_ptr": line_ptr, "_x2g_mol_ptr": mol_ptr,
              "_x2g_symmetric": bool(fl[0] == 0), "_x2g_max_degree": int(fl[1]),

@@ -802,8 +802,7 @@ class _ReadoutMLPs(torch.autograd.Function):
                 return WT[g, i].data_ptr() if grad else None
 
             # (as _ChainFn: the flat launch reads each readout's input rows row-major, no T plane 0)
-            ctx.rm0 = WGRAD_X_ROWMAJOR and grad and all(grad_sink(p) is not None
-                                                        for p in (*W1, *B1, *W2, *B2) if p is not None)
+            ctx.rm0 = WGRAD_X_ROWMAJOR and grad
             f0 = CHAIN_SILU | (CHAIN_IN0_ROWMAJOR if ctx.rm0 else 0)
             stages = [(ChainStage * 2)(ChainStage(_dp(W1[g]), _dp(B1[g]), _dp(z1[g]), None, wt(g, 0), f0),
                                        ChainStage(_dp(W2[g]), _dp(B2[g]), _dp(z2[g]), _dp(h2[g]), wt(g, 1), CHAIN_SILU))
@@ -1556,74 +1555,22 @@ class ChainBwdStage(ctypes.Structure):
                 ("flags", ctypes.c_int32)]
 
 
-class WgradJob(ctypes.Structure):
-    """x2g_wgrad_job."""
-    _fields_ = [("dy", ctypes.c_void_p), ("x", ctypes.c_void_p), ("dw", ctypes.c_void_p), ("db", ctypes.c_void_p)]
-
-
-def wgrad_batched(dys, xs, weights, biases):
-    """Weight / bias gradients of several D x D Linear layers over the same rows in one launch
-    (x2g_wgrad_batched): dW_g = dy_g^T x_g, db_g = colsum(dy_g).  Summed straight into the
-    gradient bucket when every parameter is bucket-backed (returns Nones for them then), slab sums
-    deferred inside ``deferred_wgrad()``; otherwise returns fresh (dW, db) per layer."""
-    G = len(dys)
-    R, D = dys[0].shape
-    dev = dys[0].device
-    params = list(weights) + [b for b in biases if b is not None]
-    bufs, acc = _wgrad_targets(params, [tuple(p.shape) for p in params], dev)
-    dws, rest = bufs[:G], iter(bufs[G:])
-    dbs = [next(rest) if b is not None else None for b in biases]
-    lib = _lib.load()
-    ws_bytes = int(lib.x2g_wgrad_batched_workspace(R, D, G))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    jobs = (WgradJob * G)(*[WgradJob(_dp(dys[g]), _dp(xs[g]), _dp(dws[g]), _dp(dbs[g])) for g in range(G)])
-    defer = acc and _defer() is not None
-    call("x2g_wgrad_batched", jobs, G, R, D, (ACCUM_WGRAD if acc else 0) | (DEFER_SLAB_SUM if defer else 0), ptr(ws),
-         ws_bytes, stream_ptr())
-    if defer:
-        splits = int(lib.x2g_wgrad_batched_splits(R, D, G))
-        per = ws_bytes // G
-        for g in range(G):
-            _defer_job(ws, g * per, splits, D * D, D, dws[g], dbs[g])
-    if acc:
-        return [None] * G, [None] * G
-    return dws, dbs
-
-
 def chain_wgrad(in_t, dz_t, R, weights, biases, x0=None):
-    """Weight / bias gradients of every chain stage from the T-layout operands (x2g_chain_wgrad, or
-    tiled jobs of the flat launch inside ``deferred_wgrad()`` or with ``x0``); bucket-backed parameters
-    are summed into the bucket (Nones returned for them), slab sums deferred inside ``deferred_wgrad()``.  ``x0``: the chain's input, row-major [R, D], when the forward
-    ran with CHAIN_IN0_ROWMAJOR (plane 0 of ``in_t`` is then unwritten and stage 0 reads ``x0``)."""
+    """Weight / bias gradients of every chain stage from the T-layout operands, as tiled jobs of the flat
+    launch; bucket-backed parameters are summed into the bucket (Nones returned for them), queued inside
+    ``deferred_wgrad()``.  ``x0``: the chain's input, row-major [R, D], when the forward ran with
+    CHAIN_IN0_ROWMAJOR (plane 0 of ``in_t`` is then unwritten and stage 0 reads ``x0``)."""
     n = len(weights)
-    D = weights[0].shape[1]
-    dev = in_t.device
     params = list(weights) + [b for b in biases if b is not None]
-    bufs, acc = _wgrad_targets(params, [tuple(p.shape) for p in params], dev)
+    bufs, acc = _wgrad_targets(params, [tuple(p.shape) for p in params], in_t.device)
     dws, rest = bufs[:n], iter(bufs[n:])
     dbs = [next(rest) if b is not None else None for b in biases]
-    d = _defer() if acc else None
-    if d is not None or x0 is not None:
-        tf = in_t.shape[1]
-        jobs = [TiledJob(dz_t.data_ptr() + 4 * g * tf, in_t.data_ptr() + 4 * g * tf, _dp(dws[g]), _dp(dbs[g]), 0, 0)
-                for g in range(n)]
-        if x0 is not None:
-            jobs[0] = TiledJob(dz_t.data_ptr(), x0.data_ptr(), _dp(dws[0]), _dp(dbs[0]), 0, 0, TILED_X_ROWMAJOR)
-        if d is not None:
-            # (the flat launch runs after this backward returned: x0 is kept alive with the T tensors)
-            _queue_tiled(d, R, jobs, [in_t, dz_t] + ([x0] if x0 is not None else []))
-            return [None] * n, [None] * n
-        _tiled_now(R, jobs, acc, dev)
-        if acc:
-            return [None] * n, [None] * n
-        return dws, dbs
-    lib = _lib.load()
-    ws_bytes = int(lib.x2g_chain_wgrad_workspace(R, D, n))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    dw_arr = (ctypes.c_void_p * n)(*[_dp(t) for t in dws])
-    db_arr = (ctypes.c_void_p * n)(*[_dp(t) for t in dbs])
-    call("x2g_chain_wgrad", ptr(in_t), ptr(dz_t), n, R, D, dw_arr, db_arr, ACCUM_WGRAD if acc else 0, ptr(ws),
-         ws_bytes, stream_ptr())
+    tf = in_t.shape[1]
+    jobs = [TiledJob(dz_t.data_ptr() + 4 * g * tf, in_t.data_ptr() + 4 * g * tf, _dp(dws[g]), _dp(dbs[g]), 0, 0)
+            for g in range(n)]
+    if x0 is not None:
+        jobs[0] = TiledJob(dz_t.data_ptr(), x0.data_ptr(), _dp(dws[0]), _dp(dbs[0]), 0, 0, TILED_X_ROWMAJOR)
+    _run_tiled(R, jobs, [in_t, dz_t] + ([x0] if x0 is not None else []), acc)
     if acc:
         return [None] * n, [None] * n
     return dws, dbs
@@ -1634,9 +1581,9 @@ class _ChainFn(torch.autograd.Function):
     stage s computes z_s = in_s W_s^T + b_s, out_s = act(z_s) (+ the held ResidualLayer input or
     the external residual), in_{s+1} = out_s.  Backward: one kernel for every stage's data gradient
     (x2g_chain_bwd, residual gradients folded in registers) + the weight gradients over the stage
-    inputs and dz that both kernels leave in the tiled-transposed layout: x2g_chain_wgrad for plain
-    parameters; for bucket-backed ones (a training step) tiled jobs of the flat launch, whose stage 0
-    reads the chain's row-major input (CHAIN_IN0_ROWMAJOR: the forward then writes no T plane 0)."""
+    inputs and dz that both kernels leave in the tiled-transposed layout: tiled jobs of the flat launch,
+    whose stage 0 reads the chain's row-major input (CHAIN_IN0_ROWMAJOR: the forward then writes no T
+    plane 0)."""
 
     @staticmethod
     def forward(ctx, x, res, flags, ln, *params):
@@ -1656,10 +1603,8 @@ class _ChainFn(torch.autograd.Function):
         WT = torch.empty(n, D, D, **f32) if grad else None
         in_t = torch.empty(n, tf, **f32) if grad else None
         # The chain's input stays row-major for the backward anyway (xn on the LayerNorm path, else x2), so
-        # when the weight gradients will be tiled jobs of the flat launch (bucket-backed parameters: what a
-        # training step has) stage 0's reads it there and the kernel writes no T plane 0.  x2g_chain_wgrad
-        # (plain parameters) reads contiguous T planes and keeps plane 0.
-        ctx.rm0 = WGRAD_X_ROWMAJOR and grad and all(grad_sink(p) is not None for p in params if p is not None)
+        # stage 0's weight gradient reads it there and the kernel writes no T plane 0.
+        ctx.rm0 = WGRAD_X_ROWMAJOR and grad
         fl = [flags[i] | (CHAIN_IN0_ROWMAJOR if ctx.rm0 and i == 0 else 0) for i in range(n)]
         st = (ChainStage * n)(*[ChainStage(_dp(W[i]), _dp(B[i]), _dp(zs[i]), _dp(y) if i == n - 1 else None,
                                            None if WT is None else WT[i].data_ptr(), fl[i]) for i in range(n)])
@@ -1942,16 +1887,7 @@ class _FeaturizeFn(torch.autograd.Function):
         for i in range(2):
             specs.append((dz2_t.data_ptr(), y1_t.data_ptr() + fb * i * tf, dw2.data_ptr() + fb * i * 128,
                           db2.data_ptr() if (db2 is not None and i == 0) else None, 256, 128))
-        n = len(specs)
-        d = _defer() if acc else None
-        if d is not None:
-            _queue_tiled(d, R, [TiledJob(*sp) for sp in specs], [dz1_t, dz2_t, xs_t, y1_t])
-            return None, None, None, None, None, None
-        lib = _lib.load()
-        ws_bytes = int(lib.x2g_tiled_wgrad_workspace(R, 128, n))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        jobs = (TiledJob * n)(*[TiledJob(*sp) for sp in specs])
-        call("x2g_tiled_wgrad", jobs, n, R, 128, ACCUM_WGRAD if acc else 0, ptr(ws), ws_bytes, stream_ptr())
+        _run_tiled(R, [TiledJob(*sp) for sp in specs], [dz1_t, dz2_t, xs_t, y1_t], acc)
         if acc:
             return None, None, None, None, None, None
         return None, None, dw1, db1, dw2, db2
@@ -1977,14 +1913,24 @@ WGRAD_X_ROWMAJOR = True
 
 
 def _tiled_now(R, jobs, acc, dev):
-    """The given x2g_tiled_jobs in one flat launch of their own, slab sums included (no deferral open:
-    the path of jobs with a row-major operand, which x2g_tiled_wgrad / x2g_chain_wgrad do not take)."""
+    """The given x2g_tiled_jobs in one flat launch of their own, slab sums included."""
     lib = _lib.load()
     n = len(jobs)
     ws_bytes = int(lib.x2g_tiled_wgrad_flat_workspace(R, 128, n))
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
     call("x2g_tiled_wgrad_flat", (TiledJob * n)(*jobs), n, R, 128, ACCUM_WGRAD if acc else 0, None, ptr(ws), ws_bytes,
          stream_ptr())
+
+
+def _run_tiled(R, jobs, keep, acc):
+    """Run x2g_tiled_jobs over ``R`` rows: queued on the open deferral for its flat launch when their
+    destinations are bucket-backed (``acc``) and one is open, else launched now.  ``keep``: the tensors the
+    jobs point into (a queued job runs after the backward that made it returned)."""
+    d = _defer() if acc else None
+    if d is not None:
+        _queue_tiled(d, R, jobs, keep)
+    else:
+        _tiled_now(R, jobs, acc, keep[0].device)
 
 
 class Proj(ctypes.Structure):
@@ -1998,35 +1944,18 @@ class ProjGrad(ctypes.Structure):
 
 
 def tiled_wgrad(dy_ts, x_ts, R, weights, biases, layouts=None):
-    """Weight / bias gradients of D x D Linear layers, one job per layer; bucket-backed parameters are
-    summed into the bucket (Nones returned).  Inside ``deferred_wgrad()`` the jobs are queued for its flat
-    launch and the slab sums deferred.  Otherwise: all operands in the T layout -> x2g_tiled_wgrad;
-    ``layouts`` (per job TILED_*_ROWMAJOR bits, operands given as row-major [R, D] tensors) -> a flat
-    launch of their own (x2g_tiled_wgrad_flat: x2g_tiled_wgrad takes T operands only; another row split,
-    so fp32 rounding differs from it)."""
+    """Weight / bias gradients of D x D Linear layers, one job of the flat launch per layer; bucket-backed
+    parameters are summed into the bucket (Nones returned), queued inside ``deferred_wgrad()``.
+    ``layouts``: per job TILED_*_ROWMAJOR bits for operands given as row-major [R, D] tensors (default:
+    all in the T layout)."""
     n = len(weights)
-    D = weights[0].shape[1]
-    dev = dy_ts[0].device
     params = list(weights) + [b for b in biases if b is not None]
-    bufs, acc = _wgrad_targets(params, [tuple(p.shape) for p in params], dev)
+    bufs, acc = _wgrad_targets(params, [tuple(p.shape) for p in params], dy_ts[0].device)
     dws, rest = bufs[:n], iter(bufs[n:])
     dbs = [next(rest) if b is not None else None for b in biases]
-    d = _defer() if acc else None
     lay = layouts if layouts is not None else [0] * n
-    if d is not None or any(lay):
-        jobs = [TiledJob(_dp(dy_ts[g]), _dp(x_ts[g]), _dp(dws[g]), _dp(dbs[g]), 0, 0, lay[g]) for g in range(n)]
-        if d is not None:
-            _queue_tiled(d, R, jobs, list(dy_ts) + list(x_ts))
-            return [None] * n, [None] * n
-        _tiled_now(R, jobs, acc, dev)
-        if acc:
-            return [None] * n, [None] * n
-        return dws, dbs
-    lib = _lib.load()
-    ws_bytes = int(lib.x2g_tiled_wgrad_workspace(R, D, n))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    jobs = (TiledJob * n)(*[TiledJob(_dp(dy_ts[g]), _dp(x_ts[g]), _dp(dws[g]), _dp(dbs[g])) for g in range(n)])
-    call("x2g_tiled_wgrad", jobs, n, R, D, ACCUM_WGRAD if acc else 0, ptr(ws), ws_bytes, stream_ptr())
+    jobs = [TiledJob(_dp(dy_ts[g]), _dp(x_ts[g]), _dp(dws[g]), _dp(dbs[g]), 0, 0, lay[g]) for g in range(n)]
+    _run_tiled(R, jobs, list(dy_ts) + list(x_ts), acc)
     if acc:
         return [None] * n, [None] * n
     return dws, dbs
