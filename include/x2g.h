@@ -259,9 +259,10 @@ int x2g_spherical_basis(const float* pos, const int32_t* atom_i, const int32_t* 
 
 /* S[t, :] = w_sbf[out_dim, sbf_dim] sbf[t, :] + b_sbf: lin_sbf of sbftransformer_conv.py:148,
  * materialised once per layer so the attention kernels read one row per triplet instead of
- * re-projecting it.  sbf_dim 42 (config.json's 7 x 6 basis): out_dim in {32, 64, 128, 256} on the
- * compiled narrow-K kernels; any other sbf_dim (e.g. 112, the reference's default 7 x 16) runs as
- * x2g_dense_fwd. */
+ * re-projecting it.  sbf_dim 42 (config.json's 7 x 6 basis) with out_dim 64 or 128 and 16-byte
+ * aligned sbf / sbfproj runs on its own wave kernel; every other out_dim (any positive width, e.g.
+ * 30 or 256: widths outside {32, 64, 128, 256} used to be X2G_EUNSUPPORTED), alignment or sbf_dim
+ * (e.g. 112, the reference's default 7 x 16) runs as x2g_dense_fwd. */
 int x2g_sbf_project(const float* sbf, int64_t num_triplets, int32_t sbf_dim, const float* w_sbf,
                     const float* b_sbf, int32_t out_dim, float* sbfproj, void* stream);
 
@@ -664,17 +665,23 @@ int x2g_linear_wgrad_ex(const float* dy, const float* x, int64_t rows, int32_t o
 /* Row-wise dense layer with fused epilogue: y[R,N] = act(x[R,K] w[N,K]^T + b[N]) (+ res[R,N]);
  * z[R,N] (optional) receives the pre-activation x w^T + b for the backward.  Replaces the
  * Linear -> SiLU -> add chains of residual_layer.py:21-27, model.py:39,47-50, readout.py:38-42,
- * xgnn.py:54-55,70 and the projections of sbftransformer_conv.py:99-107,127.  b, res, z may be NULL. */
+ * xgnn.py:54-55,70 and the projections of sbftransformer_conv.py:99-107,127.  b, res, z may be NULL.
+ * Two kernels: a persistent one for in/out features <= 128, in_features > 8, both multiples of 4
+ * and x / y / z / res 16-byte aligned; the general row GEMM for every other shape or alignment. */
 int x2g_dense_fwd(const float* x, const float* w, const float* b, int64_t rows, int32_t in_features,
                   int32_t out_features, int act, const float* res, float* y, float* z, void* stream);
 
-/* Workspace bytes for x2g_dense_bwd. */
+/* Workspace bytes for x2g_dense_bwd.  Like x2g_dense_bwd_splits and x2g_dense_bwd_slab_offset it
+ * answers from the shape alone (in/out features <= 128: one slab per workgroup of the persistent
+ * kernel; else the dz buffer followed by x2g_linear_wgrad_ex's slabs), never from pointers. */
 size_t x2g_dense_bwd_workspace(int64_t rows, int32_t in_features, int32_t out_features);
 
 /* Full backward of x2g_dense_fwd in one call: dz = dy * act'(z); dx = dz w (dx may be NULL: no
  * data gradient is formed); dw = dz^T x; db = colsum(dz) (db may be NULL).  For in/out features
  * <= 128 this is one persistent kernel (weight staged in LDS once per CU, dx and the per-CU
- * weight-gradient partials from the same LDS tiles) plus a fixed-order slab sum. */
+ * weight-gradient partials from the same LDS tiles; a 16-byte-vectorised form where the features
+ * are multiples of 4 and the operands aligned, a dword form with the same slab layout otherwise)
+ * plus a fixed-order slab sum; wider layers take the general row GEMM and x2g_linear_wgrad_ex. */
 int x2g_dense_bwd(const float* dy, const float* z, int act, const float* x, const float* w, int64_t rows,
                   int32_t in_features, int32_t out_features, float* dx, float* dw, float* db, void* workspace,
                   size_t workspace_bytes, void* stream);

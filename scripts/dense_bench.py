@@ -22,7 +22,10 @@ def t(fn, reps=30):
     return a.elapsed_time(b) / reps * 1e3
 
 
-for R, K, N in [(21058, 128, 128), (2304, 128, 128), (10, 128, 128), (21058, 6, 128), (21058, 338, 256)]:
+SHAPES = [(21058, 128, 128), (2304, 128, 128), (10, 128, 128), (21058, 6, 128), (21058, 42, 128), (21058, 338, 256)]
+
+# python scripts/dense_bench.py [R,K,N ...]: other shapes (one shape per profiler run keeps its kernels apart)
+for R, K, N in [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]] or SHAPES:
     x = torch.randn(R, K, device=dev)
     w = torch.randn(N, K, device=dev) * 0.1
     b = torch.randn(N, device=dev)

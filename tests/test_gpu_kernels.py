@@ -867,9 +867,9 @@ def test_flat_adam_lr_schedule_matches_lambda_lr(cuda, staircase):
 @pytest.mark.parametrize("T,out_dim", [(194060, 128), (1000, 128), (37, 128), (0, 128), (1000, 256), (37, 256),
                                        (1000, 64), (37, 32)])
 def test_sbf_project_vs_torch(cuda, T, out_dim):
-    """x2g_sbf_project: the wave-independent MFMA kernel (out_dim 128 / 64) and the VALU path
-    (out_dim 256, e.g. xgnn_poly's default in_channels=256, xgnn.py:16; and 32).  T = 37 makes 37*42
-    floats, not a multiple of 4: the last 16-byte chunk is partial."""
+    """x2g_sbf_project: the wave-independent MFMA kernel (out_dim 128 / 64) and the general dense
+    forward (out_dim 256, e.g. xgnn_poly's default in_channels=256, xgnn.py:16; and 32).  T = 37 makes
+    37*42 floats, not a multiple of 4: the last 16-byte chunk is partial."""
     from x2gnn._lib import call, ptr, stream_ptr
 
     g = torch.Generator(device=cuda).manual_seed(T + 5 + out_dim)
@@ -909,7 +909,9 @@ def test_sbf_project_batch_equals_per_layer(cuda, T, out_dim, n):
 @pytest.mark.gpu
 def test_sbf_project_rows_independent_of_nonfinite_neighbours(cuda):
     """A non-finite sbf row poisons only its own projection (the reference's lin_sbf is row-wise):
-    the narrow-K kernel's LDS span has row stride K, so a row's pad columns alias the next row."""
+    a kernel that pads the 42-wide contraction over contiguous sbf rows must mask the pad columns,
+    which alias the next row's first floats (a zero weight alone would turn Inf / NaN into NaN).
+    Width 128, aligned: the wave kernel."""
     from x2gnn._lib import call, ptr, stream_ptr
 
     T = 200
@@ -946,6 +948,171 @@ def test_dense_narrow_k_vs_torch(cuda, R, K):
     y = ops.dense(x, w, b, act=ops.ACT_SILU, res=res)
     ref = torch.nn.functional.silu(x.double() @ w.double().t() + b.double()) + res.double()
     torch.testing.assert_close(y.double(), ref, rtol=1e-5, atol=1e-5)
+
+
+_GUARD = 8  # guard floats before and after a carved tensor (32 bytes: the carve stays 16-byte aligned)
+
+
+class _Carved:
+    """A [shape] float32 tensor inside a larger NaN-filled buffer, `off` floats past 16-byte
+    alignment, with guard elements on both sides that a kernel must leave untouched."""
+
+    def __init__(self, shape, dev, off=0, fill=float("nan"), data=None):
+        n = int(np.prod(shape))
+        self.buf = torch.full((2 * _GUARD + off + n,), float("nan"), device=dev)
+        assert self.buf.data_ptr() % 16 == 0
+        self.t = self.buf[_GUARD + off:_GUARD + off + n].view(*shape)
+        self.lo, self.hi = self.buf[:_GUARD + off], self.buf[_GUARD + off + n:]
+        if data is not None:
+            self.t.copy_(data)
+        else:
+            self.t.fill_(fill)
+
+    def guards_intact(self):
+        return bool(torch.isnan(self.lo).all() and torch.isnan(self.hi).all())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("R,K,N", [(33, 128, 128), (65, 12, 20), (65, 128, 6), (1, 6, 128)])
+def test_dense_fwd_routes_by_alignment(cuda, R, K, N):
+    """x2g_dense_fwd has two kernels: dense_fwd_v6 (K, N <= 128, K > 8, both multiples of 4, every
+    operand 16-byte aligned) and dense_rows (everything else).  One pointer one float off alignment
+    alone sends the call to dense_rows: every such call, and the aligned one, against fp64, and
+    against each other where the aligned call takes v6.  33 rows: one past v6's 32-row tile, inside
+    dense_rows' 64-row tile; (65, 12, 20) / (65, 128, 6): a partial column tile, N % 4 != 0."""
+    from x2gnn._lib import call, ptr, stream_ptr
+
+    g = torch.Generator(device=cuda).manual_seed(R + 3 * K + 5 * N)
+    x0 = torch.randn(R, K, device=cuda, generator=g)
+    w = torch.randn(N, K, device=cuda, generator=g) / np.sqrt(K)
+    b = torch.randn(N, device=cuda, generator=g)
+    res0 = torch.randn(R, N, device=cuda, generator=g)
+    zref = x0.double() @ w.double().t() + b.double()
+    tol = dict(rtol=1e-5, atol=1e-5)
+    for act in (0, 1):
+        for with_res in (False, True):
+            yref = (torch.nn.functional.silu(zref) if act else zref) + (res0.double() if with_res else 0.0)
+            for with_z in (False, True):
+                names = ["x", "y"] + (["z"] if with_z else []) + (["res"] if with_res else [])
+                aligned = None
+                for odd in [None] + names:  # None: every pointer aligned
+                    x = _Carved((R, K), cuda, off=int(odd == "x"), data=x0)
+                    res = _Carved((R, N), cuda, off=int(odd == "res"), data=res0) if with_res else None
+                    y = _Carved((R, N), cuda, off=int(odd == "y"))
+                    z = _Carved((R, N), cuda, off=int(odd == "z")) if with_z else None
+                    call("x2g_dense_fwd", ptr(x.t), ptr(w), ptr(b), R, K, N, act, ptr(res.t if res else None),
+                         ptr(y.t), ptr(z.t if z else None), stream_ptr())
+                    what = f"act {act} res {with_res} z {with_z} misaligned {odd}"
+                    torch.testing.assert_close(y.t.double(), yref, msg=lambda m: f"y, {what}: {m}", **tol)
+                    if with_z:
+                        torch.testing.assert_close(z.t.double(), zref, msg=lambda m: f"z, {what}: {m}", **tol)
+                    for c in (x, res, y, z):
+                        assert c is None or c.guards_intact(), what
+                    assert torch.equal(x.t, x0) and (res is None or torch.equal(res.t, res0)), what
+                    if odd is None:
+                        aligned = (y.t.clone(), z.t.clone() if with_z else None)
+                    else:  # the two routes (or the same route twice) agree
+                        torch.testing.assert_close(y.t, aligned[0], msg=lambda m: f"y routes, {what}: {m}", **tol)
+                        if with_z:
+                            torch.testing.assert_close(z.t, aligned[1], msg=lambda m: f"z routes, {what}: {m}", **tol)
+
+
+@pytest.mark.gpu
+def test_sbf_project_general_path_vs_torch(cuda):
+    """x2g_sbf_project outside its wave kernel (sbf_dim 42, out_dim 64 / 128, aligned) runs as the
+    general dense forward: other widths (96; 30, not a multiple of 4 and refused before), width 128
+    with sbf or the output one float off alignment, and row isolation at width 32 (non-finite
+    entries in a tile's interior, on both sides of the 64-row tile boundary and in the last row)."""
+    from x2gnn._lib import call, ptr, stream_ptr
+
+    g = torch.Generator(device=cuda).manual_seed(42)
+
+    def run(T, D, sbf_off=0, out_off=0, bad=()):
+        sbf0 = torch.randn(T, 42, device=cuda, generator=g)
+        for r, c, v in bad:
+            sbf0[r, c] = v
+        w = torch.randn(D, 42, device=cuda, generator=g) / 6.5
+        b = torch.randn(D, device=cuda, generator=g)
+        sbf = _Carved((T, 42), cuda, off=sbf_off, data=sbf0)
+        out = _Carved((T, D), cuda, off=out_off)
+        call("x2g_sbf_project", ptr(sbf.t), T, 42, ptr(w), ptr(b), D, ptr(out.t), stream_ptr())
+        assert sbf.guards_intact() and out.guards_intact()
+        assert torch.equal(sbf.t.view(torch.int32), sbf0.view(torch.int32))  # bitwise: NaN entries too
+        return out.t, sbf0.double() @ w.double().t() + b.double()
+
+    for T, D, so, oo in [(37, 96, 0, 0), (37, 30, 0, 0), (37, 128, 1, 0), (37, 128, 0, 1)]:
+        out, ref = run(T, D, so, oo)
+        torch.testing.assert_close(out.double(), ref, rtol=1e-5, atol=1e-5, msg=lambda m: f"{T, D, so, oo}: {m}")
+    inf, nan = float("inf"), float("nan")
+    bad = [(5, 0, inf), (63, 1, -inf), (64, 0, nan), (64, 41, nan), (129, 3, inf)]
+    out, ref = run(130, 32, bad=bad)
+    good = torch.ones(130, dtype=torch.bool, device=cuda)
+    good[[r for r, _, _ in bad]] = False
+    assert torch.isfinite(out[good]).all() and not torch.isfinite(out[~good]).any()
+    torch.testing.assert_close(out[good].double(), ref[good], rtol=1e-5, atol=1e-5)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_db", [False, True])
+@pytest.mark.parametrize("R,K,N", [(1, 6, 128), (70, 6, 128), (70, 6, 64), (70, 128, 4), (70, 130, 20)])
+def test_dense_bwd_ex_deferred_slab_sum(cuda, R, K, N, with_db):
+    """x2g_dense_bwd_ex with X2G_ACCUM_WGRAD | X2G_DEFER_SLAB_SUM leaves dw / db alone and its
+    partials where x2g_dense_bwd_slab_offset / x2g_dense_bwd_splits say; one x2g_slab_job built from
+    them as ops._defer_job builds it, summed by x2g_slab_sum_batch(accum = 1), gives the plain
+    call's dw / db plus the prefilled constants bit for bit, and the same dx.  K <= 8 and N <= 8:
+    dense_bwd_persist<64> (the workspace queries answer in its slabs); (70, 130, 20): the general
+    path, slabs after the dz buffer.  A workspace one byte short is refused, nothing written."""
+    from x2gnn import _lib, ops
+    from x2gnn._lib import ptr, stream_ptr
+
+    lib = _lib.load()
+    g = torch.Generator(device=cuda).manual_seed(R + 3 * K + 5 * N)
+    x = torch.randn(R, K, device=cuda, generator=g)
+    w = torch.randn(N, K, device=cuda, generator=g) / np.sqrt(K)
+    wsb = int(lib.x2g_dense_bwd_workspace(R, K, N))
+    splits, offset = int(lib.x2g_dense_bwd_splits(R, K, N)), int(lib.x2g_dense_bwd_slab_offset(R, K, N))
+    assert splits >= 1 and offset + 4 * splits * (N * K + (N if with_db else 0)) <= wsb
+    for act in (0, 1):
+        z = torch.randn(R, N, device=cuda, generator=g)
+        dy = torch.randn(R, N, device=cuda, generator=g)
+
+        def run(flags, fill_w, fill_b, ws_bytes=wsb):
+            ws = torch.zeros(wsb, dtype=torch.uint8, device=cuda)
+            dx, dw = _Carved((R, K), cuda), _Carved((N, K), cuda, fill=fill_w)
+            db = _Carved((N,), cuda, fill=fill_b) if with_db else None
+            rc = lib.x2g_dense_bwd_ex(ptr(dy), ptr(z), act, ptr(x), ptr(w), R, K, N, ptr(dx.t), None, ptr(dw.t),
+                                      ptr(db.t if db else None), flags, ptr(ws), ws_bytes, stream_ptr())
+            return rc, ws, dx, dw, db
+
+        nan = float("nan")
+        rc, _, dx, dw, db = run(0, nan, nan, ws_bytes=wsb - 1)
+        assert rc == 1003  # X2G_EWORKSPACE
+        assert all(bool(torch.isnan(c.buf).all()) for c in (dx, dw, db) if c is not None)
+
+        rc, _, dx0, dw0, db0 = run(0, nan, nan)
+        assert rc == 0
+        zd, sg = z.double(), torch.sigmoid(z.double())
+        dz = dy.double() * (sg * (1 + zd * (1 - sg)) if act else 1.0)
+        wtol = dict(rtol=1e-4, atol=1e-4 * max(1.0, np.sqrt(R / 100)))  # test_dense_fused_vs_torch's
+        torch.testing.assert_close(dx0.t.double(), dz @ w.double(), rtol=1e-4, atol=1e-4)
+        torch.testing.assert_close(dw0.t.double(), dz.t() @ x.double(), **wtol)
+        if with_db:
+            torch.testing.assert_close(db0.t.double(), dz.sum(0), **wtol)
+
+        rc, ws, dx1, dw1, db1 = run(ops.ACCUM_WGRAD | ops.DEFER_SLAB_SUM, 0.5, -0.25)
+        assert rc == 0
+        assert torch.equal(dw1.t, torch.full_like(dw1.t, 0.5))  # deferred: not yet summed
+        assert db1 is None or torch.equal(db1.t, torch.full_like(db1.t, -0.25))
+        base = ws.data_ptr() + offset
+        job = ops.SlabJob(base, base + 4 * splits * N * K if with_db else None, dw1.t.data_ptr(),
+                          db1.t.data_ptr() if with_db else None, N * K, N if with_db else 0, splits, 0, 0)
+        assert lib.x2g_slab_sum_batch((ops.SlabJob * 1)(job), 1, 1, stream_ptr()) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(dx1.t, dx0.t)
+        assert torch.equal(dw1.t, dw0.t + 0.5)
+        assert db1 is None or torch.equal(db1.t, db0.t - 0.25)
+        for c in (dx0, dw0, db0, dx1, dw1, db1):
+            assert c is None or c.guards_intact()
 
 
 @pytest.mark.parametrize("E", [0, 1, 3000])

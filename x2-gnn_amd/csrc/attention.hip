@@ -730,28 +730,6 @@ __global__ void __launch_bounds__(256) attn_bwd_src_kernel(
 
 #include "attention_fold.inc"
 
-// ------------------------------------------------------------------------------ sbf projection
-// S[t, :] = W sbf_t + b for all triplets (x2g_sbf_project): one wave per triplet row (grid-
-// stride), CPL channels per lane with W in registers, the 42-float sbf row wave-uniform (scalar
-// loads), one coalesced row store.  Every attention kernel then reads S rows instead of
-// re-projecting (3 x 84 FMAs per triplet and lane, and 84 weight VGPRs, saved per layer).
-template <int CPL>
-__global__ void __launch_bounds__(256) sbf_project_kernel(const float* __restrict__ sbf, const float* __restrict__ w,
-                                                          const float* __restrict__ b, int64_t T, int D,
-                                                          float* __restrict__ S) {
-  const int lane = threadIdx.x & 63;
-  const bool act = lane * CPL < D;
-  const int c0 = act ? lane * CPL : 0;
-  float wr[CPL][kS], br[CPL];
-  load_weights<CPL>(w, b, c0, act, wr, br);
-  const int64_t nw = static_cast<int64_t>(gridDim.x) * kAttnWaves;
-  for (int64_t t = uniform(blockIdx.x * kAttnWaves + (threadIdx.x >> 6)); t < T; t += nw) {
-    float sp[CPL];
-    sbf_project<CPL>(wr, br, sbf + t * kS, sp);
-    store_row<CPL>(S + t * D + c0, act, sp);
-  }
-}
-
 // ------------------------------------------------------------------------------ dispatch
 enum class Pass { kFwd, kBwdDst, kBwdSrc };
 
@@ -930,20 +908,16 @@ X2G_API int x2g_sbf_attention_bwd_src(const float* q, const float* sbf, const fl
   return dispatch(Pass::kBwdSrc, a, heads, channels, sbf_dim, as_stream(stream));
 }
 
-namespace x2g {  // csrc/dense.hip: the narrow-K MFMA dense forward
-int dense_fwd_narrow_launch(const float* x, const float* w, const float* b, const float* res, int64_t R, int K, int N,
-                            int act, float* y, float* z, hipStream_t st);
-}  // namespace x2g
-
 namespace x2g {
-// S = sbf W^T + b for the 42-wide sbf rows, wave-independent: a wave takes 16-row blocks of sbf
+// S = sbf W^T + b for the 42-wide sbf rows (x2g_sbf_project; every attention kernel then reads S
+// rows instead of re-projecting), wave-independent: a wave takes 16-row blocks of sbf
 // (held as the MFMA B operand, lane (i, g) = row i, k = 16q + 4g + e as two 8-byte loads: the
 // 168-byte rows are 8-byte aligned) and produces all 16 NOB output columns with
 // v_mfma_f32_16x16x4_f32 against W^T fragments staged once per workgroup in LDS (the A operand,
 // read as one conflict-free 16-byte chunk per lane and group); D lane (i, g) holds the block's
 // row i, columns 16 ob + 4g .. +3: one 16-byte store each.  No barriers after the staging, the next
 // block's rows in flight during the MFMAs: the loads, MFMAs and stores of the 4-5 resident waves
-// per SIMD overlap (the tile-staged dense_fwd_narrow serialised them per workgroup: 3.1 TB/s).
+// per SIMD overlap (a kernel staging whole tiles per workgroup serialised them: 3.1 TB/s).
 constexpr int kSPQ = 3;  // 16-wide contraction groups (K = 42 -> 48, zero-padded)
 
 // Round 3: the same wave-independent MFMA product with both HBM streams made line-coalesced (the
@@ -1134,20 +1108,8 @@ X2G_API int x2g_sbf_project(const float* sbf, int64_t T, int32_t sbf_dim, const 
       sbf_project_waves<4><<<static_cast<unsigned>(want), kSPWaves * 64, 0, st>>>(sbf, w_sbf, b_sbf, T, sbfproj);
     return last_launch_status();
   }
-  // f32 MFMA, tiles staged through LDS (dense.hip): that kernel covers N <= 128 output columns
-  // and addresses rows with 32-bit offsets; wider projections take the per-row kernel below
-  if (out_dim % 4 == 0 && out_dim <= 128 && T * 128 * 4 < (int64_t(1) << 31) &&
-      reinterpret_cast<uintptr_t>(sbf) % 16 == 0 && reinterpret_cast<uintptr_t>(sbfproj) % 16 == 0)
-    return dense_fwd_narrow_launch(sbf, w_sbf, b_sbf, nullptr, T, kS, out_dim, 0, sbfproj, nullptr, st);
-  int64_t want = (T + kAttnWaves - 1) / kAttnWaves;
-  const unsigned blocks = static_cast<unsigned>(want < 4096 ? want : 4096);
-  switch (out_dim) {
-    case 32: case 64: sbf_project_kernel<1><<<blocks, 256, 0, st>>>(sbf, w_sbf, b_sbf, T, out_dim, sbfproj); break;
-    case 128: sbf_project_kernel<2><<<blocks, 256, 0, st>>>(sbf, w_sbf, b_sbf, T, out_dim, sbfproj); break;
-    case 256: sbf_project_kernel<4><<<blocks, 256, 0, st>>>(sbf, w_sbf, b_sbf, T, out_dim, sbfproj); break;
-    default: return X2G_EUNSUPPORTED;
-  }
-  return last_launch_status();
+  // every other width or alignment: the general dense forward
+  return x2g_dense_fwd(sbf, w_sbf, b_sbf, T, kS, out_dim, 0, nullptr, sbfproj, nullptr, stream);
 }
 
 X2G_API int x2g_sbf_project_batch(const float* sbf, int64_t T, int32_t sbf_dim, const float* const* w_sbf,

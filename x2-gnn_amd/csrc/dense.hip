@@ -9,9 +9,21 @@
 // and the backward's data gradient is one kernel too:
 //      dZ = dY * act'(Z) (written out for the weight gradient),   dX = dZ W.
 //
-// Tiling: a 256-thread workgroup owns 64 rows x 128 output columns; wave w computes columns
-// 32w..32w+31 for two 32-row MFMA tiles (v_mfma_f32_32x32x2_f32, exact fp32).  K is streamed in
-// 32-wide chunks through LDS with the next chunk prefetched into registers during the MFMAs.
+//
+// No training or inference step of the benched configurations launches these kernels any more (the
+// row chains, conv_proj, feat, table_chain, rbf_gate and readout_head kernels took their layers);
+// they serve the drop-in ops.dense / ops.linear API, the fallbacks in ops.py, x2g_sbf_project for
+// the shapes its wave kernel does not take, and the benchmark's dense probes.  Five paths, all
+// v_mfma_f32_32x32x2_f32 (exact fp32):
+//   forward   dense_fwd_v6       K, N <= 128, K > 8, K % 4 == N % 4 == 0, 16-byte aligned x / y / z / res
+//             dense_rows<true>   everything else: any shape, any alignment.  A 256-thread workgroup
+//                                owns 64 rows x 128 columns, K streamed through LDS in 32-wide chunks
+//   backward  dense_bwd_v8       K, N <= 128, N > 8, K % 4 == N % 4 == 0, 16-byte aligned operands
+//             dense_bwd_persist  every other call with K, N <= 128 (same slab layout as v8, so the
+//                                choice may depend on pointers; the workspace queries do not)
+//             general            larger shapes: dense_rows<false> (dz and dx) or silu_grad_elementwise
+//                                (dz alone), then x2g_linear_wgrad_ex
+// plus the batched forms of v6 / v8 and the fused ResidualLayer forward (residual_fwd_kernel).
 #include <math.h>
 
 #include "common.hpp"
@@ -30,6 +42,9 @@ enum Act { kActNone = 0, kActSilu = 1 };
 
 __device__ __forceinline__ float sigmoidf_(float z) { return 1.0f / (1.0f + expf(-z)); }
 
+// The general row GEMM: a 256-thread workgroup owns 64 rows x 128 output columns; wave w computes
+// columns 32w..32w+31 for two 32-row MFMA tiles.  K is streamed in 32-wide chunks through LDS with
+// the next chunk prefetched into registers during the MFMAs.
 // B operand element (k, n): BT -> stored as Bm[n][k] (a torch Linear weight [N, K]),
 // else Bm[k][n] (the same weight read as [K', N'] for the data gradient).
 template <bool BT, int ACT_IN>
@@ -139,16 +154,16 @@ __global__ void __launch_bounds__(256) dense_rows(const float* __restrict__ A, c
 
 
 // ------------------------------------------------------------------------------------------------
-// Persistent forms for the common case K <= 128 and N <= 128 (every 128x128 layer, lin_rbf with
-// K = 6, the readout head with N = 1): the weight is staged into LDS ONCE per workgroup (one
-// 8-wave workgroup per CU) and the waves walk row tiles with the next tile's loads in flight.
+// Persistent forms for K <= 128 and N <= 128 (every 128x128 layer, lin_rbf with K = 6, the readout
+// head with N = 1): the weight is staged into LDS ONCE per workgroup and the waves walk row tiles
+// with the next tile's loads in flight.
 //
 // MFMA v_mfma_f32_32x32x2_f32, step s: lane l = (h = l >> 5, i = l & 31) supplies A[i][c] and
 // B[c][i'] for contraction index c = cmap(s, h).  Any bijection works as long as A and B agree:
 //   STEPS = 64 (c < 128): c = 64 h + s  -> a lane's A values are 64 CONTIGUOUS floats of one row;
-//   STEPS = 4  (c < 8)  : c = 2 s + h.
-// The weight lives in LDS in "slot" layout: B[cmap(s, h)][j] at (s * 128 + j) * 2 + h, so a B
-// fragment is 64 consecutive floats (no bank conflicts, no padding).
+//   STEPS = 4           : c = 2 s + h   (dense_bwd_persist, for any s < 64).
+// dense_bwd_persist keeps the weight in LDS in "slot" layout: B[cmap(s, h)][j] at
+// (s * 128 + j) * 2 + h, so a B fragment is 64 consecutive floats (no bank conflicts, no padding).
 template <int STEPS>
 __device__ __forceinline__ int cmap(int s, int h) { return STEPS == 64 ? 64 * h + s : 2 * s + h; }
 
@@ -179,263 +194,17 @@ __device__ __forceinline__ void wslot_store(float* __restrict__ ws, const float 
   }
 }
 
-// 16 values of a row-major [R, N] matrix in the MFMA C/D layout of rows [r0, r0+32), column n
-// (rows clamped, so the loads are unconditional).
-__device__ __forceinline__ void cfrag_load(const float* __restrict__ m, int64_t r0, int64_t R, int N, int n,
-                                           float (&v)[16]) {
-  const int lane = threadIdx.x & 63;
-  // 32-bit offsets (the host guarantees R * max(K, N) < 2^31): 64-bit addresses hoisted out of
-  // the tile loop would not fit in the register budget
-  const int nc = n < N ? n : N - 1;
-  const int rb = static_cast<int>(r0) + 4 * (lane >> 5), rmax = static_cast<int>(R) - 1;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const int r = rb + (j & 3) + 8 * (j >> 2);
-    v[j] = ld_pin(m + ((r < rmax ? r : rmax) * N + nc));
-  }
-}
-
-// ---------------------------------------------------------------------------------- forward
-constexpr int kPTile = 32;     // forward rows per tile
-constexpr int kPFwdGrid = 256;  // one 8-wave workgroup per CU
-
-// A fragment of rows [r0, r0+32) straight from global memory into registers: a[s] = X[row][cmap(s,h)]
-// (rows and columns clamped: a clamped column meets a zero weight, a clamped row is not stored).
-template <int STEPS, bool VEC>
-__device__ __forceinline__ void afrag_load(const float* __restrict__ X, int64_t r0, int64_t R, int K,
-                                           float (&a)[STEPS]) {
-  const int lane = threadIdx.x & 63, h = lane >> 5;
-  const int r = static_cast<int>(r0) + (lane & 31), rmax = static_cast<int>(R) - 1;
-  const float* row = X + (r < rmax ? r : rmax) * K;
-  if (STEPS == 64 && VEC) {  // 16 float4 per lane (K % 4 == 0, 16-byte aligned rows)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int c = 64 * h + 4 * i;
-      const float4 v = *reinterpret_cast<const float4*>(row + (c + 4 <= K ? c : K - 4));
-      a[4 * i] = v.x;
-      a[4 * i + 1] = v.y;
-      a[4 * i + 2] = v.z;
-      a[4 * i + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < STEPS; ++s) {
-      const int c = cmap<STEPS>(s, h);
-      a[s] = ld_pin(row + (c < K ? c : K - 1));
-    }
-  }
-}
-
-template <int STEPS, bool VEC>
-__device__ __forceinline__ void fwd_tile(const float* __restrict__ Ws, const float* __restrict__ X,
-                                         const float* __restrict__ res, int64_t t, int64_t R, int K, int N, int act,
-                                         int n, float bn, float* __restrict__ Y, float* __restrict__ Z) {
-  const int lane = threadIdx.x & 63, h = lane >> 5;
-  float a[STEPS], rv[16];
-  afrag_load<STEPS, VEC>(X, t * kPTile, R, K, a);
-  if (res) cfrag_load(res, t * kPTile, R, N, n, rv);
-  floatx16 acc0, acc1;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    acc0[j] = 0.f;
-    acc1[j] = 0.f;
-  }
-  const float* wb = Ws + n * 2 + h;
-#pragma unroll
-  for (int s = 0; s < STEPS; s += 2) {
-    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], wb[s * 256], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s + 1], wb[(s + 1) * 256], acc1, 0, 0, 0);
-  }
-  const int rbase = static_cast<int>(t) * kPTile + 4 * h;
-  if (n < N) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int r = rbase + (j & 3) + 8 * (j >> 2);
-      const float zv = acc0[j] + acc1[j] + bn;
-      float v = act == kActSilu ? zv / (1.0f + expf(-zv)) : zv;
-      if (res) v += rv[j];
-      if (r < R) {
-        if (Z) Z[r * N + n] = zv;
-        Y[r * N + n] = v;
-      }
-    }
-  }
-}
-
-// y = act(x w^T + b) (+ res), z = x w^T + b.  8 waves: wave w computes output columns
-// 32 (w & 3).. of every other 32-row tile (tile slot w >> 2), its A operand loaded from global
-// memory straight into registers, its B operand read from the LDS weight.  After the weight is
-// staged the waves never synchronise: with two waves per SIMD one multiplies while the other
-// waits for its tile.
-template <int STEPS, bool VEC>
-__global__ void __launch_bounds__(512) dense_fwd_persist(const float* __restrict__ X, const float* __restrict__ W,
-                                                         const float* __restrict__ bias,
-                                                         const float* __restrict__ res, int64_t R, int K, int N,
-                                                         int act, float* __restrict__ Y, float* __restrict__ Z) {
-  __shared__ __attribute__((aligned(16))) float Ws[64 * 128 * 2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n = 32 * (wave & 3) + (lane & 31);
-  const int64_t ntiles = (R + kPTile - 1) / kPTile;
-  const int64_t step = 2 * static_cast<int64_t>(gridDim.x);
-  const float bn = (bias && n < N) ? bias[n] : 0.f;
-  {
-    float wv[32];
-    wslot_load<STEPS, true, 512>(W, N, K, wv);
-    wslot_store<512>(Ws, wv);
-    __syncthreads();
-  }
-  for (int64_t t = 2 * static_cast<int64_t>(blockIdx.x) + (wave >> 2); t < ntiles; t += step)
-    fwd_tile<STEPS, VEC>(Ws, X, res, t, R, K, N, act, n, bn, Y, Z);
-}
-
-// ---------------------------------------------------------------- forward, LDS-staged x tiles
-// The same product for K % 4 == 0 (every trunk layer), with x staged through LDS in full
-// 512-byte rows instead of fragment-shaped loads (lane-per-row 16-byte loads touch 64 cache
-// lines per instruction and load the tile once per column wave: texture-address bound).
-//   * 8 waves, two 32-row tiles per iteration (slot = wave >> 2), wave w -> columns 32 (w & 3)..;
-//   * the next tile pair is loaded into registers (4 x 16 B per thread, coalesced rows) while the
-//     current pair is multiplied, then written to the other LDS buffer (double buffered);
-//   * LDS x tile: row r, 16-byte chunk q at chunk position q ^ (r & 15) — writes of 16
-//     consecutive chunks and the A-fragment reads (lane = row, chunk 16h + g) are both
-//     conflict-free; a lane's ds_read_b128 yields A values for 4 consecutive MFMA steps
-//     (c = 64h + 4g .. 64h + 4g + 3, the cmap<64> order of the slot-layout weight);
-//   * residual fragments for the current pair are loaded before the next pair's tile loads, so
-//     waiting for them never drains the prefetch.
-
-__device__ __forceinline__ void xpair_load(const float* __restrict__ X, int64_t tp, int64_t R, int K,
-                                           float4 (&v)[4]) {
-  const int kc = K >> 2;  // valid chunks per row
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int idx = threadIdx.x + 512 * u, row = idx >> 5, q = idx & 31;
-    const int r = static_cast<int>(tp) * 64 + row, rmax = static_cast<int>(R) - 1;
-    v[u] = *reinterpret_cast<const float4*>(X + (r < rmax ? r : rmax) * K + 4 * (q < kc ? q : kc - 1));
-  }
-}
-
-__device__ __forceinline__ void xpair_store(float* __restrict__ buf, const float4 (&v)[4]) {
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int idx = threadIdx.x + 512 * u, row = idx >> 5, q = idx & 31;
-    *reinterpret_cast<float4*>(buf + row * 128 + 4 * (q ^ (row & 15))) = v[u];
-  }
-}
-
-__global__ void __launch_bounds__(512) dense_fwd_staged(const float* __restrict__ X, const float* __restrict__ W,
-                                                        const float* __restrict__ bias,
-                                                        const float* __restrict__ res, int64_t R, int K, int N,
-                                                        int act, float* __restrict__ Y, float* __restrict__ Z) {
-  __shared__ __attribute__((aligned(16))) float Ws[64 * 128 * 2];
-  __shared__ __attribute__((aligned(16))) float Xs[2][64 * 128];  // [buffer][slot*32 + row][128]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, i = lane & 31;
-  const int slot = wave >> 2;
-  const int n = 32 * (wave & 3) + i;
-  const int64_t npairs = (R + 63) / 64;
-  const int64_t G = gridDim.x;
-  const float bn = (bias && n < N) ? bias[n] : 0.f;
-  int64_t tp = blockIdx.x;
-  float4 stage[4];
-  {
-    float wv[32];
-    wslot_load<64, true, 512>(W, N, K, wv);
-    xpair_load(X, tp, R, K, stage);
-    wslot_store<512>(Ws, wv);
-    xpair_store(Xs[0], stage);
-    if (tp + G < npairs) xpair_load(X, tp + G, R, K, stage);
-    __syncthreads();
-  }
-  const float* wb = Ws + n * 2 + h;
-  for (int it = 0; tp < npairs; tp += G, ++it) {
-    const float* xs = Xs[it & 1] + (slot * 32 + i) * 128;
-    const int t = static_cast<int>(tp) * 2 + slot;  // this wave's 32-row tile
-    float rv[16];
-    if (res) cfrag_load(res, static_cast<int64_t>(t) * kPTile, R, N, n, rv);
-    // the pair after next: write the staged pair to the other buffer, then refill the registers
-    const bool more = tp + G < npairs;
-    if (more) xpair_store(Xs[(it + 1) & 1], stage);
-    if (tp + 2 * G < npairs) xpair_load(X, tp + 2 * G, R, K, stage);
-    floatx16 acc0, acc1;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      acc0[j] = 0.f;
-      acc1[j] = 0.f;
-    }
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const float4 a = *reinterpret_cast<const float4*>(xs + 4 * ((16 * h + g) ^ (i & 15)));
-      const int s = 4 * g;
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, wb[s * 256], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, wb[(s + 1) * 256], acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, wb[(s + 2) * 256], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, wb[(s + 3) * 256], acc1, 0, 0, 0);
-    }
-    const int rbase = t * kPTile + 4 * h;
-    if (n < N) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int r = rbase + (j & 3) + 8 * (j >> 2);
-        const float zv = acc0[j] + acc1[j] + bn;
-        float v = act == kActSilu ? zv / (1.0f + expf(-zv)) : zv;
-        if (res) v += rv[j];
-        if (r < R) {
-          if (Z) Z[r * N + n] = zv;
-          Y[r * N + n] = v;
-        }
-      }
-    }
-    __syncthreads();  // the next buffer is complete; this one is free for the pair after next
-  }
-}
-
-// ---------------------------------------------------------------- forward helpers (v5 design, used by v6)
-// dense_fwd_staged plus the two fixes its phase measurements called for (R = 21k rows: weight
-// staging 5.6 us, epilogue stores 6.3 us of 40 us):
-//   * the weight is read row-contiguous (coalesced) and written to a slot layout padded to 258
-//     floats per slot: 2-way bank conflicts on the staging writes, conflict-free B reads;
-//   * the epilogue goes through LDS: the C fragments (one column, 16 rows per lane) are written
-//     into the consumed x buffer, then every thread handles whole 16-byte row chunks: bias,
-//     activation, residual (loaded row-wise and early), and 16-byte stores of z and y
-//     (4x fewer store instructions than per-lane dword stores, which are issue-bound).
-constexpr int kSlotStride = 258;
-
-__device__ __forceinline__ void wpad_load(const float* __restrict__ W, int N, int K, float (&v)[32]) {
-#pragma unroll
-  for (int u = 0; u < 32; ++u) {
-    const int idx = threadIdx.x + 512 * u, n = idx >> 7, k = idx & 127;
-    const float x = ld_pin(W + (n < N ? n : N - 1) * K + (k < K ? k : K - 1));
-    v[u] = (n < N && k < K) ? x : 0.f;
-  }
-}
-
-__device__ __forceinline__ void wpad_store(float* __restrict__ ws, const float (&v)[32]) {
-#pragma unroll
-  for (int u = 0; u < 32; ++u) {
-    const int idx = threadIdx.x + 512 * u, n = idx >> 7, k = idx & 127;
-    ws[(k & 63) * kSlotStride + 2 * n + (k >> 6)] = v[u];  // B[c=k][j=n], cmap<64>: c = 64h + s
-  }
-}
-
-// 64 rows x 128 columns of a row-major [R, N] matrix (N % 4 == 0) in the x-pair thread mapping.
-__device__ __forceinline__ void rows_load(const float* __restrict__ m, int64_t tp, int64_t R, int N,
-                                          float4 (&v)[4]) {
-  const int nc = N >> 2;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int idx = threadIdx.x + 512 * u, row = idx >> 5, q = idx & 31;
-    const int r = static_cast<int>(tp) * 64 + row, rmax = static_cast<int>(R) - 1;
-    v[u] = *reinterpret_cast<const float4*>(m + (r < rmax ? r : rmax) * N + 4 * (q < nc ? q : nc - 1));
-  }
-}
+// ---------------------------------------------------------------- helpers shared by v6, v8 and the fused ResidualLayer
+constexpr int kSlotStride = 258;  // v8's weight slots, padded: conflict-free B reads, 2-way staging writes
 
 typedef float f4 __attribute__((ext_vector_type(4)));  // native vector: loads/stores stay in registers
 
+// A tile's staging on named registers: a float4[4] carried across the tile loop with a
+// conditional refill stayed a private (scratch) array.
 struct Stage4 {
   f4 v0, v1, v2, v3;
 };
 
-// The tile-pair staging on named registers: a float4[4] carried across the tile loop with a
-// conditional refill stayed a private (scratch) array.  Chunk u of this thread: row
-// (tid >> 5) + 16 u of the pair, 16-byte column chunk tid & 31.
 template <int U>
 __device__ __forceinline__ f4 st_get(const Stage4& st) {
   if constexpr (U == 0) return st.v0;
@@ -444,52 +213,13 @@ __device__ __forceinline__ f4 st_get(const Stage4& st) {
   else return st.v3;
 }
 
-__device__ __forceinline__ void xpair_load4(const float* __restrict__ X, int64_t tp, int64_t R, int K, Stage4& st) {
-  const int kc = K >> 2, q = threadIdx.x & 31, qc = 4 * (q < kc ? q : kc - 1);
-  const int rmax = static_cast<int>(R) - 1, r0 = static_cast<int>(tp) * 64 + (threadIdx.x >> 5);
-  const int ra = r0 < rmax ? r0 : rmax, rb = r0 + 16 < rmax ? r0 + 16 : rmax;
-  const int rc = r0 + 32 < rmax ? r0 + 32 : rmax, rd = r0 + 48 < rmax ? r0 + 48 : rmax;
-  st.v0 = *reinterpret_cast<const f4*>(X + ra * K + qc);
-  st.v1 = *reinterpret_cast<const f4*>(X + rb * K + qc);
-  st.v2 = *reinterpret_cast<const f4*>(X + rc * K + qc);
-  st.v3 = *reinterpret_cast<const f4*>(X + rd * K + qc);
-}
-
-__device__ __forceinline__ void xpair_store4(float* __restrict__ buf, const Stage4& st) {
-  const int q = threadIdx.x & 31, row = threadIdx.x >> 5;  // rows row, +16, +32, +48 share (row & 15)
-  float* p = buf + row * 128 + 4 * (q ^ (row & 15));
-  *reinterpret_cast<f4*>(p) = st.v0;
-  *reinterpret_cast<f4*>(p + 16 * 128) = st.v1;
-  *reinterpret_cast<f4*>(p + 32 * 128) = st.v2;
-  *reinterpret_cast<f4*>(p + 48 * 128) = st.v3;
-}
-
 __device__ __forceinline__ float act_apply(float z, int act) { return act == kActSilu ? z / (1.0f + expf(-z)) : z; }
 
-// Row-wise epilogue of one 16-byte chunk (row (tid >> 5) + 16 U of the pair): bias, activation,
-// residual, 16-byte stores of z and y.
-template <int U>
-__device__ __forceinline__ void epi_chunk(const float* __restrict__ buf, const Stage4& rres, f4 b4, int64_t tp,
-                                          int64_t R, int N, int act, float* __restrict__ Y, float* __restrict__ Z) {
-  const int q = threadIdx.x & 31, row = (threadIdx.x >> 5) + 16 * U;
-  const int r = static_cast<int>(tp) * 64 + row;
-  const f4 zc = *reinterpret_cast<const f4*>(buf + row * 128 + 4 * (q ^ (row & 15))) + b4;
-  const f4 rr = st_get<U>(rres);
-  f4 yv;
-  yv.x = act_apply(zc.x, act) + rr.x;
-  yv.y = act_apply(zc.y, act) + rr.y;
-  yv.z = act_apply(zc.z, act) + rr.z;
-  yv.w = act_apply(zc.w, act) + rr.w;
-  if (r < R && 4 * q < N) {
-    if (Z) *reinterpret_cast<f4*>(Z + r * N + 4 * q) = zc;
-    *reinterpret_cast<f4*>(Y + r * N + 4 * q) = yv;
-  }
-}
-
 // ---------------------------------------------------------------------------------- backward
-// Backward of dense_fwd_persist, fused: dz = dy * act'(z); dx = dz w (if dx != NULL); partial
-// weight / bias gradients dz^T x and colsum(dz) over the workgroup's tiles, written to slab
-// blockIdx.x (summed afterwards in a fixed order).  8 waves, 64-row tiles staged through LDS
+// The fused backward for K, N <= 128 at any alignment (v8's stand-in, same slab layout):
+// dz = dy * act'(z); dx = dz w (if dx != NULL); partial weight / bias gradients dz^T x and
+// colsum(dz) over the workgroup's tiles, written to slab blockIdx.x (summed afterwards in a fixed
+// order; a workgroup without a tile writes zeros).  8 waves, 64-row tiles staged through LDS
 // with row stride 130 (32 rows at columns c, c+1: 64 distinct banks; rows r and r+16 over 32
 // consecutive columns: 64 distinct banks):
 //   dx: wave w -> rows 32 (w >> 2).., k columns 32 (w & 3)..   (cmap c = 2s + h)
@@ -644,11 +374,19 @@ __global__ void __launch_bounds__(512) dense_bwd_persist(const float* __restrict
 }
 
 // ---------------------------------------------------------------- forward, v6: two workgroups per CU
-// 4 waves and 80 KB of LDS per workgroup (weight 64 KB + one 32-row x tile 16 KB), so two
-// workgroups share a CU and one multiplies while the other loads / stores: at 21k rows the
-// busiest CU then holds 3 tiles of 32 rows instead of 2 pairs of 64 (v5).  The weight slot
-// layout is unpadded with an XOR swizzle instead: B[c(s,h)][j] at s*256 + 2 (j ^ (s & 31)) + h
-// (staging writes 2-way, B reads conflict-free).
+// K % 4 == 0, N % 4 == 0, 16-byte aligned operands (every trunk layer).  4 waves and 80 KB of LDS
+// per workgroup (weight 64 KB + one 32-row x tile 16 KB), so two workgroups share a CU and one
+// multiplies while the other loads / stores: at 21k rows the busiest CU holds 3 tiles of 32 rows.
+//   * x is staged through LDS in full 512-byte rows (coalesced 16-byte loads, the next tile in
+//     registers during the MFMAs): row r, 16-byte chunk q at chunk position q ^ (r & 15), so the
+//     staging writes and the A-fragment reads (lane = row, chunk 16h + g) are conflict-free and one
+//     ds_read_b128 yields A values for 4 consecutive MFMA steps (c = 64h + 4g .. +3, cmap<64>);
+//   * the weight is read row-contiguous into slots with an XOR swizzle: B[c(s,h)][j] at
+//     s*256 + 2 (j ^ (s & 31)) + h (staging writes 2-way, B reads conflict-free);
+//   * the epilogue goes through LDS: the C fragments (one column, 16 rows per lane) are written
+//     into the consumed x buffer, then every thread handles whole 16-byte row chunks: bias,
+//     activation, residual (loaded row-wise and early, so waiting for it never drains the
+//     prefetch), and 16-byte stores of z and y.
 __device__ __forceinline__ int wswz(int s, int j, int h) { return s * 256 + 2 * (j ^ (s & 31)) + h; }
 
 __device__ __forceinline__ void xtile_load(const float* __restrict__ X, int64_t t, int64_t R, int K, Stage4& st) {
@@ -917,243 +655,19 @@ __global__ void __launch_bounds__(256, 1) residual_fwd_kernel(const float* __res
   }
 }
 
-// ---------------------------------------------------------------- forward, narrow K (K % 4 != 0)
-// For rows too narrow / odd for 16-byte row chunks (lin_sbf: K = 42): a 64-row tile pair is one
-// contiguous span of 64*K floats, read with 16-byte loads regardless of K and scattered into
-// LDS unchanged (row stride K, 16-byte writes); the MFMA operand read strides by K.  Contraction order
-// c(s, h) = 4 (s >> 1) + 2h + (s & 1): a lane's two consecutive steps read one 8-byte pair.
-// Weight in the padded slot layout with the same order; epilogue as dense_fwd_v5.
-__device__ __forceinline__ int cmap_n(int s, int h) { return 4 * (s >> 1) + 2 * h + (s & 1); }
-
-template <int STEPS>
-__global__ void __launch_bounds__(512) dense_fwd_narrow(const float* __restrict__ X, const float* __restrict__ W,
-                                                        const float* __restrict__ bias,
-                                                        const float* __restrict__ res, int64_t R, int K, int N,
-                                                        int act, float* __restrict__ Y, float* __restrict__ Z) {
-  constexpr int KP = 2 * STEPS;  // padded row length (>= K, multiple of 4)
-  __shared__ __attribute__((aligned(16))) float Ws[STEPS * kSlotStride];
-  __shared__ __attribute__((aligned(16))) float Xs[64 * 128];  // x tile [64][KP], then the output tile
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, i = lane & 31;
-  const int slot = wave >> 2;
-  const int n = 32 * (wave & 3) + i;
-  const int q = tid & 31;
-  const int64_t npairs = (R + 63) / 64;
-  const int64_t G = gridDim.x;
-  f4 b4 = {0.f, 0.f, 0.f, 0.f};
-  if (bias && 4 * q < N) b4 = f4{bias[4 * q], bias[4 * q + 1], bias[4 * q + 2], bias[4 * q + 3]};
-  // weight: B[c][j] = w[j][c] for c < K, zero beyond
-  for (int idx = tid; idx < STEPS * 2 * 128; idx += 512) {
-    const int j = idx / (2 * STEPS), r = idx - j * 2 * STEPS;  // r = contraction index c
-    const int sl = 2 * (r >> 2) + (r & 1), hh = (r >> 1) & 1;
-    const float wv = (j < N && r < K) ? W[j * K + r] : 0.f;
-    Ws[sl * kSlotStride + 2 * j + hh] = wv;
-  }
-  const float* wb = Ws + 2 * n + h;
-  const int nq = (64 * K) >> 2;
-  // register double buffer: the next pair's x span is in flight while this pair's MFMAs and
-  // epilogue run (NQI 16-byte chunks per thread cover 64 rows x KP floats)
-  constexpr int NQI = (16 * KP + 511) / 512;
-  f4 pre[NQI];
-  auto prefetch = [&](int64_t tpn) {
-    const int64_t bn = tpn * 64 * K;
-    const int64_t nv = ((R - tpn * 64) < 64 ? (R - tpn * 64) : 64) * K;
-#pragma unroll
-    for (int u = 0; u < NQI; ++u) {
-      const int qi = tid + 512 * u;
-      // whole 16-byte chunks load as one vector; the span's last partial chunk (64*K or the
-      // ragged tail's length need not be a multiple of 4) element-wise, never past the end of X
-      if (qi < nq && 4 * qi + 4 <= nv) {
-        pre[u] = *reinterpret_cast<const f4*>(X + bn + 4 * qi);
-      } else {
-        pre[u] = f4{0.f, 0.f, 0.f, 0.f};
-        if (qi < nq && 4 * qi < nv)
-          for (int e = 0; e < 4; ++e)
-            if (4 * qi + e < nv) pre[u][e] = X[bn + 4 * qi + e];
-      }
-    }
-  };
-  if (blockIdx.x < npairs) prefetch(blockIdx.x);
-  for (int64_t tp = blockIdx.x; tp < npairs; tp += G) {
-    // stage the pair: rows [64 tp, 64 tp + 64) are floats [64 tp K, 64 tp K + 64 K)
-    const int64_t nvalid = ((R - tp * 64) < 64 ? (R - tp * 64) : 64) * K;
-    __syncthreads();  // previous pair's output tile fully stored
-#pragma unroll
-    for (int u = 0; u < NQI; ++u) {  // the span lands as-is (row stride K): one 16-byte LDS write
-      const int qi = tid + 512 * u;
-      if (qi < nq) {
-        f4 v = pre[u];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (4 * qi + e >= nvalid) v[e] = 0.f;
-        *reinterpret_cast<f4*>(Xs + 4 * qi) = v;
-      }
-    }
-    // contraction columns K..KP-1 of a row fall on the next row's first floats: the operand read
-    // below masks them (a zero weight alone would turn a neighbour's Inf/NaN into NaN here)
-    if (tid < KP - K) Xs[64 * K + tid] = 0.f;
-    __syncthreads();
-    if (tp + G < npairs) prefetch(tp + G);
-    floatx16 acc0, acc1;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      acc0[j] = 0.f;
-      acc1[j] = 0.f;
-    }
-    const float* xs = Xs + (slot * 32 + i) * K + 2 * h;
-    const int klim = K - 2 * h;  // contraction index 4g + 2h (+1) must stay below K
-#pragma unroll
-    for (int g = 0; g < STEPS / 2; ++g) {
-      const float a0 = 4 * g < klim ? xs[4 * g] : 0.f, a1 = 4 * g + 1 < klim ? xs[4 * g + 1] : 0.f;
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, wb[(2 * g) * kSlotStride], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, wb[(2 * g + 1) * kSlotStride], acc1, 0, 0, 0);
-    }
-    __syncthreads();  // x tile consumed: the buffer stages the output
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int r = slot * 32 + (j & 3) + 8 * (j >> 2) + 4 * h;
-      Xs[r * 128 + 4 * ((n >> 2) ^ (r & 15)) + (n & 3)] = acc0[j] + acc1[j];
-    }
-    __syncthreads();
-    Stage4 rres{};
-    if (res) xpair_load4(res, tp, R, N, rres);
-    epi_chunk<0>(Xs, rres, b4, tp, R, N, act, Y, Z);
-    epi_chunk<1>(Xs, rres, b4, tp, R, N, act, Y, Z);
-    epi_chunk<2>(Xs, rres, b4, tp, R, N, act, Y, Z);
-    epi_chunk<3>(Xs, rres, b4, tp, R, N, act, Y, Z);
-  }
-}
-
-int dense_fwd_narrow_launch(const float* x, const float* w, const float* b, const float* res, int64_t R, int K, int N,
-                            int act, float* y, float* z, hipStream_t st) {
-  // the kernel covers N <= 128 columns and K <= 2*64; row offsets are 32-bit
-  if (N > 128 || K > 128 || R * 128 * 4 >= (int64_t(1) << 31)) return X2G_EUNSUPPORTED;
-  const int64_t npairs = (R + 63) / 64;
-  const unsigned grid = static_cast<unsigned>(npairs < 512 ? npairs : 512);
-  if (K <= 44)
-    dense_fwd_narrow<22><<<grid, 512, 0, st>>>(x, w, b, res, R, K, N, act, y, z);
-  else
-    dense_fwd_narrow<64><<<grid, 512, 0, st>>>(x, w, b, res, R, K, N, act, y, z);
-  return last_launch_status();
-}
-
-// ---------------------------------------------------------------- backward, narrow input (K <= 8)
-// The radial-basis layers (lin_rbf: 6 -> 128, sbftransformer_conv.py:99, readout.py:38) have
-// almost no data gradient to compute: dx[r, 0:K] = dz[r, :] w[:, 0:K] is K dot products of
-// length N per row.  One wave per row (grid-stride): lane holds CPL = N/64 channels of dz,
-// forms its K partial products, and a 64-lane xor reduction leaves dx[r, k] in every lane;
-// dW[n, k] += dz[r, n] x[r, k] accumulates in registers (x row wave-uniform: scalar loads),
-// db[n] += dz[r, n].  Waves fold their partials through LDS into one slab per workgroup.
-template <int CPL, int KMAX>
-__global__ void __launch_bounds__(256) dense_bwd_narrow(const float* __restrict__ dY, const float* __restrict__ Zin,
-                                                        const float* __restrict__ X, const float* __restrict__ W,
-                                                        int64_t R, int K, int N, int act, float* __restrict__ dX,
-                                                        const float* __restrict__ dXadd, float* __restrict__ part_w,
-                                                        float* __restrict__ part_b) {
-  __shared__ float red[4][64 * CPL * (KMAX + 1)];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c0 = lane * CPL;
-  float wr[CPL][KMAX];
-#pragma unroll
-  for (int j = 0; j < CPL; ++j)
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) wr[j][k] = (c0 + j < N && k < K) ? W[(c0 + j) * K + k] : 0.f;
-  float gw[CPL][KMAX], gb[CPL];
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) {
-    gb[j] = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) gw[j][k] = 0.f;
-  }
-  // four rows per iteration (rows r, r + nw, r + 2nw, r + 3nw) so their loads are in flight together
-  constexpr int ROWS = 4;
-  const int64_t nw = static_cast<int64_t>(gridDim.x) * 4;
-  for (int64_t r0 = uniform(blockIdx.x * 4 + wave); r0 < R; r0 += ROWS * nw) {
-    float d[ROWS][CPL], xr[ROWS][KMAX];
-#pragma unroll
-    for (int u = 0; u < ROWS; ++u) {
-      const int64_t r = r0 + u * nw;
-      const bool rok = r < R;
-      const int64_t rc = rok ? r : R - 1;
-#pragma unroll
-      for (int j = 0; j < CPL; ++j) {
-        const bool ok = rok && c0 + j < N;
-        float v = dY[rc * N + (c0 + j < N ? c0 + j : N - 1)];
-        if (act == kActSilu) {
-          const float z = Zin[rc * N + (c0 + j < N ? c0 + j : N - 1)];
-          const float sg = 1.0f / (1.0f + expf(-z));
-          v *= sg * (1.0f + z * (1.0f - sg));
-        }
-        d[u][j] = ok ? v : 0.f;
-      }
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) xr[u][k] = (k < K) ? keep(X[rc * K + (k < K ? k : 0)], rok) : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < ROWS; ++u) {
-      const int64_t r = r0 + u * nw;
-      float px[KMAX];
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) {
-        float acc = 0.f;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) {
-          acc = fmaf(d[u][j], wr[j][k], acc);
-          gw[j][k] = fmaf(d[u][j], xr[u][k], gw[j][k]);
-        }
-        px[k] = group_sum<64>(acc);
-      }
-#pragma unroll
-      for (int j = 0; j < CPL; ++j) gb[j] += d[u][j];
-      if (dX && lane < K && r < R) {
-        float v = 0.f;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) v = lane == k ? px[k] : v;
-        if (dXadd) v += dXadd[r * K + lane];
-        dX[r * K + lane] = v;
-      }
-    }
-  }
-  // fold the 4 waves (fixed order) and write this workgroup's slab
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) {
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) red[wave][(c0 + j) * (KMAX + 1) + k] = gw[j][k];
-    red[wave][(c0 + j) * (KMAX + 1) + KMAX] = gb[j];
-  }
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-      const int n = c0 + j;
-      if (n >= N) continue;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) {
-        const int o = n * (KMAX + 1) + k;
-        if (k < K) part_w[static_cast<int64_t>(blockIdx.x) * N * K + n * K + k] =
-            ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
-      }
-      const int o = n * (KMAX + 1) + KMAX;
-      if (part_b) part_b[static_cast<int64_t>(blockIdx.x) * N + n] = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
-    }
-  }
-}
-
-constexpr int kNarrowBwdGrid = 512;
-
-static inline bool dense_narrow_bwd(int64_t R, int32_t K, int32_t N) {
-  return R > 0 && K <= 8 && N <= 128 && N > 64 && N % 64 == 0;
-}
-
-// ---------------------------------------------------------------- backward helpers (v5 design, used by v8)
-// dense_bwd_persist restructured like the v5 forward (K % 4 == 0, N % 4 == 0, 16-byte aligned):
-//   * dy, z, x tiles (64 rows) are read with 16-byte loads (4 per thread per matrix instead of
-//     16 dword loads) into registers, the next tile's loads fly during the MFMAs;
+// ---------------------------------------------------------------- backward, v8: 32-row tiles
+// dense_bwd_persist restructured like the v6 forward (K % 4 == 0, N % 4 == 0, 16-byte aligned):
+//   * dy, z, x tiles are read with 16-byte loads into registers, the next tile's loads fly during
+//     the MFMAs;
 //   * LDS: weight in the padded slot layout (cmap<64>, B[c = n][j = k] = w[n][k], staged from
-//     coalesced rows), dz and x tiles in the chunk-swizzled [64][128] layout: dx's A fragments
+//     coalesced rows), dz and x tiles in the chunk-swizzled [32][128] layout: dx's A fragments
 //     are ds_read_b128 (4 MFMA steps each) and dW's row pairs (r, r ^ 8) hit disjoint banks;
-//   * dx leaves through LDS (transposed into the consumed x tile) as 16-byte row stores.
-// 8 waves: dx wave w -> rows 32 (w >> 2).., k columns 32 (w & 3)..;
-//          dW wave w -> n rows 32 (w & 3).., k columns 64 (w >> 2)...
+//   * dx leaves through LDS as 16-byte row stores.
+// The work is split by wave role: waves 0-3 compute the tile's dx (32 rows x 32 columns each),
+// waves 4-7 its dW contribution (32 n-rows x all K columns each, over the tile's 32 rows).  Each
+// SIMD then holds one dx wave and one dW wave (64 MFMAs each per tile), and the 32-row granularity
+// balances the chip: at 21k rows 658 tiles over 220 workgroups (<= 3 tiles each, 10.2 us of MFMA
+// per CU) instead of 330 64-row tiles over 165 (2 x 6.8 us).
 __device__ __forceinline__ int swz(int r, int c) { return r * 128 + 4 * ((c >> 2) ^ (r & 15)) + (c & 3); }
 
 __device__ __forceinline__ void wpad_load_bwd(const float* __restrict__ W, int N, int K, float (&v)[32]) {
@@ -1184,27 +698,12 @@ __device__ __forceinline__ f4 silu_grad4(f4 d, f4 z) {
   return o;
 }
 
-// rows >= R and columns >= cols of a staged tile are zeroed on the way into LDS
-__device__ __forceinline__ f4 mask4(f4 v, int64_t tp, int U, int64_t R, int cols) {
-  const int q = threadIdx.x & 31, row = (threadIdx.x >> 5) + 16 * U;
-  const bool ok = tp * 64 + row < R && 4 * q < cols;
-  return ok ? v : f4{0.f, 0.f, 0.f, 0.f};
-}
-
 struct DenseBwdBatch {
   x2g_dense_bwd_group g[X2G_MAX_GROUPS];
   float* part_w[X2G_MAX_GROUPS];
   float* part_b[X2G_MAX_GROUPS];
 };
 
-// ---------------------------------------------------------------- backward, v8: 32-row tiles
-// As v5 (weight in the padded slot layout, dz and x tiles chunk-swizzled in LDS, next tile
-// prefetched into registers during the MFMAs, dx through LDS as 16-byte row stores), but on
-// 32-row tiles with the work split by wave role: waves 0-3 compute the tile's dx (32 rows x 32
-// columns each, K = N), waves 4-7 its dW contribution (32 n-rows x all K columns each, over the
-// tile's 32 rows).  Each SIMD then holds one dx wave and one dW wave (64 MFMAs each per tile), and
-// the 32-row granularity balances the chip: at 21k rows 658 tiles over 220 workgroups (<= 3
-// tiles each, 10.2 us of MFMA per CU) instead of 330 64-row tiles over 165 (2 x 6.8 us).
 struct Stage2 {
   f4 v0, v1;
 };
@@ -1380,27 +879,16 @@ X2G_API int x2g_dense_fwd(const float* x, const float* w, const float* b, int64_
   if (R == 0) return X2G_OK;
   if (!x || !w || !y) return X2G_EINVAL;
   hipStream_t st = as_stream(stream);
-  if (K <= 128 && N <= 128 && R * 128 * 4 < (int64_t(1) << 31)) {
-    const int64_t ntiles = (R + kPTile - 1) / kPTile;
-    const int64_t want = (ntiles + 1) / 2;
-    const unsigned grid = static_cast<unsigned>(want < kPFwdGrid ? want : kPFwdGrid);
-    const bool vec = K % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0;
-    if (K <= 8)
-      dense_fwd_persist<4, false><<<grid, 512, 0, st>>>(x, w, b, res, R, K, N, act, y, z);
-    else if (!vec && K % 4 != 0 && N % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(z) && aligned16(res))
-      return dense_fwd_narrow_launch(x, w, b, res, R, K, N, act, y, z, st);
-    else if (vec && N % 4 == 0 && aligned16(y) && aligned16(z) && aligned16(res)) {
-      // v6: two 256-thread workgroups per CU.  (A register-resident-weight variant with one tile
-      // per workgroup measured no faster: at 21k rows the layer is bound by its 43 MB of
-      // x / res / y / z traffic plus the launch ramp, not by the weight staging.)
-      const unsigned g6 = static_cast<unsigned>(ntiles < 512 ? ntiles : 512);
-      dense_fwd_v6<<<g6, 256, 0, st>>>(x, w, b, res, R, K, N, act, y, z);
-    } else if (vec)
-      dense_fwd_staged<<<grid, 512, 0, st>>>(x, w, b, res, R, K, N, act, y, z);
-    else
-      dense_fwd_persist<64, false><<<grid, 512, 0, st>>>(x, w, b, res, R, K, N, act, y, z);
+  // v6: two 256-thread workgroups per CU, 32-bit offsets inside.  (A register-resident-weight
+  // variant with one tile per workgroup measured no faster: at 21k rows the layer is bound by its
+  // 43 MB of x / res / y / z traffic plus the launch ramp, not by the weight staging.)
+  if (K <= 128 && N <= 128 && K > 8 && K % 4 == 0 && N % 4 == 0 && R * 128 * 4 < (int64_t(1) << 31) &&
+      aligned16(x) && aligned16(y) && aligned16(z) && aligned16(res)) {
+    const int64_t ntiles = (R + 31) / 32;
+    dense_fwd_v6<<<static_cast<unsigned>(ntiles < 512 ? ntiles : 512), 256, 0, st>>>(x, w, b, res, R, K, N, act, y, z);
     return last_launch_status();
   }
+  // any other shape or alignment
   dim3 grid(static_cast<unsigned>((R + kDenseRows - 1) / kDenseRows), (N + kDenseCols - 1) / kDenseCols);
   dense_rows<true, kActNone><<<grid, 256, 0, st>>>(x, w, b, res, nullptr, R, K, N, act, y, z, nullptr);
   return last_launch_status();
@@ -1452,15 +940,8 @@ static inline bool dense_persistent_bwd(int64_t R, int32_t K, int32_t N) {
   return K <= 128 && N <= 128 && R > 0 && R * 128 * 4 < (int64_t(1) << 31);  // 32-bit offsets inside
 }
 
-static inline int64_t narrow_bwd_grid(int64_t R) {
-  const int64_t want = (R + 15) / 16;  // >= 4 rows per wave
-  return want < kNarrowBwdGrid ? (want > 0 ? want : 1) : kNarrowBwdGrid;
-}
-
 X2G_API size_t x2g_dense_bwd_workspace(int64_t R, int32_t K, int32_t N) {
   if (R <= 0 || K <= 0 || N <= 0) return 0;
-  if (dense_narrow_bwd(R, K, N))
-    return static_cast<size_t>(narrow_bwd_grid(R)) * (static_cast<int64_t>(N) * K + N) * sizeof(float);
   if (dense_persistent_bwd(R, K, N)) {
     const int64_t g = bwd_grid(R);
     return static_cast<size_t>(g) * (static_cast<int64_t>(N) * K + N) * sizeof(float);
@@ -1491,20 +972,9 @@ X2G_API int x2g_dense_bwd_ex(const float* dy, const float* z, int act, const flo
   }
   if (!dy || !x || !w || (act == kActSilu && !z)) return X2G_EINVAL;
   if (!workspace || workspace_bytes < x2g_dense_bwd_workspace(R, K, N)) return X2G_EWORKSPACE;
-  if (dense_narrow_bwd(R, K, N)) {
-    const int grid = static_cast<int>(narrow_bwd_grid(R));
-    float* part_w = static_cast<float*>(workspace);
-    float* part_b = db ? part_w + static_cast<int64_t>(grid) * N * K : nullptr;
-    if (N == 128)
-      dense_bwd_narrow<2, 8><<<grid, 256, 0, st>>>(dy, z, x, w, R, K, N, act, dx, dx_add, part_w, part_b);
-    else
-      dense_bwd_narrow<1, 8><<<grid, 256, 0, st>>>(dy, z, x, w, R, K, N, act, dx, dx_add, part_w, part_b);
-    int rc = last_launch_status();
-    if (rc) return rc;
-    if (flags & X2G_DEFER_SLAB_SUM) return X2G_OK;
-    return sum_slabs_launch(part_w, static_cast<int64_t>(N) * K, part_b, N, grid, dw, db, accum, st);
-  }
   if (dense_persistent_bwd(R, K, N)) {
+    // v8 and its stand-in for other shapes / alignments write the same bwd_grid(R) slabs: the
+    // workspace queries answer from (R, K, N) alone, so the pointers may only pick between these two
     const int grid = static_cast<int>(bwd_grid(R));
     float* part_w = static_cast<float*>(workspace);
     float* part_b = db ? part_w + static_cast<int64_t>(grid) * N * K : nullptr;
@@ -1512,8 +982,6 @@ X2G_API int x2g_dense_bwd_ex(const float* dy, const float* z, int act, const flo
                      aligned16(dx) && aligned16(dx_add);
     if (vec)
       dense_bwd_v8<<<grid, 512, 0, st>>>(dy, z, x, w, R, K, N, act, dx, dx_add, part_w, part_b);
-    else if (N <= 8)
-      dense_bwd_persist<4><<<grid, 512, 0, st>>>(dy, z, x, w, R, K, N, act, dx, dx_add, part_w, part_b);
     else
       dense_bwd_persist<64><<<grid, 512, 0, st>>>(dy, z, x, w, R, K, N, act, dx, dx_add, part_w, part_b);
     int rc = last_launch_status();
@@ -1546,7 +1014,6 @@ X2G_API int32_t x2g_linear_wgrad_splits(int64_t R, int32_t O, int32_t I);
 // slab count of a deferred x2g_dense_bwd_ex; the general path's slabs follow its dz buffer
 X2G_API int32_t x2g_dense_bwd_splits(int64_t R, int32_t K, int32_t N) {
   if (R <= 0 || K <= 0 || N <= 0) return 0;
-  if (dense_narrow_bwd(R, K, N)) return static_cast<int32_t>(narrow_bwd_grid(R));
   if (dense_persistent_bwd(R, K, N)) return static_cast<int32_t>(bwd_grid(R));
   return x2g_linear_wgrad_splits(R, N, K);
 }
