@@ -1058,7 +1058,7 @@ def test_sbf_project_general_path_vs_torch(cuda):
 def test_dense_bwd_ex_deferred_slab_sum(cuda, R, K, N, with_db):
     """x2g_dense_bwd_ex with X2G_ACCUM_WGRAD | X2G_DEFER_SLAB_SUM leaves dw / db alone and its
     partials where x2g_dense_bwd_slab_offset / x2g_dense_bwd_splits say; one x2g_slab_job built from
-    them as ops._defer_job builds it, summed by x2g_slab_sum_batch(accum = 1), gives the plain
+    them as ops._WGradDest.queue builds it, summed by x2g_slab_sum_batch(accum = 1), gives the plain
     call's dw / db plus the prefilled constants bit for bit, and the same dx.  K <= 8 and N <= 8:
     dense_bwd_persist<64> (the workspace queries answer in its slabs); (70, 130, 20): the general
     path, slabs after the dz buffer.  A workspace one byte short is refused, nothing written."""
@@ -2618,3 +2618,362 @@ def _lib_mod():
     from x2gnn import _lib
 
     return _lib.load()
+
+
+# ------------------------------------------------- weight-gradient destinations (ops._WGradDest)
+# Where each entry's flag word stands among its arguments, counted from the end: most end (flags, workspace,
+# workspace bytes, stream); the batched gate and the flat launches also hand a slab-job array over.
+_WGRAD_FLAG_ARG = {"x2g_edge_basis_freq_grad": -4, "x2g_sbf_radial_wgrad": -4, "x2g_linear_wgrad_ex": -4,
+                   "x2g_dense_bwd_ex": -4, "x2g_conv_proj_bwd_gate": -4, "x2g_rbf_gate_bwd": -4,
+                   "x2g_readout_head_bwd": -4, "x2g_readout_head_pool_bwd": -4, "x2g_dense_bwd_batched": -4,
+                   "x2g_rbf_gate_bwd_batch": -5, "x2g_tiled_wgrad_flat": -5, "x2g_tiled_wgrad_flat_rows": -5,
+                   "x2g_embedding_table_bwd": -2}
+_POOL_SIZES = [5, 3, 0, 6, 4, 2, 7, 1, 9]  # 37 rows in 9 segments, one of them empty
+
+
+def _wgrad_flags(seen, *names):
+    """[(entry, flag word)] of the recorded weight-gradient launches (of ``names``, when given)."""
+    return [(n, a[_WGRAD_FLAG_ARG[n]]) for n, a in seen if n in (names or _WGRAD_FLAG_ARG)]
+
+
+def _pool_index(cuda):
+    rowptr = np.concatenate([[0], np.cumsum(_POOL_SIZES)]).astype(np.int32)
+    owner = torch.from_numpy(np.repeat(np.arange(len(_POOL_SIZES)), _POOL_SIZES)).to(cuda)
+    return owner, torch.from_numpy(rowptr).to(cuda)
+
+
+def _leaf(t):
+    return t.detach().clone().requires_grad_(True)
+
+
+def _case_dense(cuda, mp, R, K, N):
+    from x2gnn import ops
+
+    lin = torch.nn.Linear(K, N).to(cuda)
+    x, gy = torch.randn(R, K, device=cuda), torch.randn(R, N, device=cuda)
+    return list(lin.parameters()), lambda: ops.dense(_leaf(x), lin.weight, lin.bias, ops.ACT_SILU).backward(gy)
+
+
+def _case_residual(cuda, mp):
+    from x2gnn import ops
+
+    l0, l1 = torch.nn.Linear(128, 128).to(cuda), torch.nn.Linear(128, 128).to(cuda)
+    x, gy = torch.randn(37, 128, device=cuda), torch.randn(37, 128, device=cuda)
+    return [l0.weight, l0.bias, l1.weight, l1.bias], lambda: ops.residual_layer(
+        _leaf(x), l0.weight, l0.bias, l1.weight, l1.bias).backward(gy)
+
+
+def _case_row_chain(cuda, mp, R):
+    from x2gnn import ops
+
+    lins = [torch.nn.Linear(128, 128).to(cuda), torch.nn.Linear(128, 128, bias=False).to(cuda)]
+    x, gy = torch.randn(R, 128, device=cuda), torch.randn(R, 128, device=cuda)
+    flags = [ops.CHAIN_SILU | ops.CHAIN_HOLD, ops.CHAIN_SILU | ops.CHAIN_RES_HELD]
+    assert ops.chain_supported(x, lins)
+    return [p for m in lins for p in m.parameters()], lambda: ops.row_chain(_leaf(x), None, lins, flags).backward(gy)
+
+
+def _case_table_chain(cuda, mp):
+    from x2gnn import ops
+    from x2gnn.layers import Linear
+
+    lins = [Linear(128, 128).to(cuda), Linear(128, 128, bias=False).to(cuda)]  # an inner stage, then a leaf
+    x, gy = 0.5 * torch.randn(5, 128, device=cuda), torch.randn(5, 128, device=cuda)
+    assert ops.table_chain_supported(x, lins)
+    return [p for m in lins for p in m.parameters()], lambda: ops.table_chain(
+        _leaf(x), [(lins[0], ops.ACT_SILU, -1), (lins[1], ops.ACT_NONE, 0)])[1].backward(gy)
+
+
+def _case_featurize(cuda, mp):
+    from x2gnn import ops
+    from x2gnn.layers import Linear
+
+    x, env = 0.3 * torch.randn(37, 258, device=cuda), torch.rand(37, device=cuda) + 0.5
+    l1, l2 = Linear(258, 256).to(cuda), Linear(256, 128).to(cuda)
+    gy = torch.randn(37, 128, device=cuda)
+    assert ops.featurize_supported(x, env, l1, l2)
+    return [l1.weight, l1.bias, l2.weight, l2.bias], lambda: ops.featurize(x, env, l1, l2).backward(gy)
+
+
+def _case_conv_proj(cuda, mp, D):
+    from x2gnn import ops
+
+    x, rbf = torch.randn(37, D, device=cuda), torch.rand(37, 6, device=cuda)
+    wr = torch.nn.Parameter(torch.randn(D, 6, device=cuda) / 2)
+    lins = [torch.nn.Linear(D, D).to(cuda) for _ in range(4)]
+    gs = [torch.randn(37, D, device=cuda) for _ in range(4)]
+    assert ops.conv_proj_fused_supported(x, rbf, [m.weight for m in lins], [m.bias for m in lins]) == (D == 128)
+    wb = [p for m in lins for p in (m.weight, m.bias)]
+    return [wr] + wb, lambda: torch.autograd.backward(ops.conv_projections(_leaf(x), _leaf(rbf), wr, *wb), gs)
+
+
+def _case_rbf_pool(cuda, mp, jobs):
+    from x2gnn import ops
+
+    owner, rowptr = _pool_index(cuda)
+    n_seg = len(_POOL_SIZES)
+    rbf = torch.randn(37, 6, device=cuda)
+    xs = [torch.randn(37, 128, device=cuda) for _ in range(max(jobs, 1))]
+    lins = [torch.nn.Linear(6, 128).to(cuda) for _ in xs]
+    gys = [torch.randn(n_seg, 128, device=cuda) for _ in xs]
+    params = [p for m in lins for p in m.parameters()]
+    if jobs == 0:  # the single pool
+        return params, lambda: ops.rbf_pool(_leaf(xs[0]), _leaf(rbf), lins[0].weight, lins[0].bias, owner, rowptr,
+                                            n_seg).backward(gys[0])
+    assert ops.rbf_pool_batch_supported(xs, rbf, [m.weight for m in lins])
+    return params, lambda: torch.autograd.backward(ops.rbf_pool_batch(
+        [_leaf(x) for x in xs], _leaf(rbf), [m.weight for m in lins], [m.bias for m in lins], owner, rowptr, n_seg), gys)
+
+
+def _case_readout(cuda, mp, D, pool):
+    from x2gnn import ops
+    from x2gnn.layers import _mlp
+
+    mlps = [_mlp(D, 1, 3).to(cuda) for _ in range(2)]
+    feats = [torch.randn(37, D, device=cuda) for _ in range(2)]
+    assert ops.readout_mlps_supported(feats, mlps)
+    pool = (_pool_index(cuda)[1], len(_POOL_SIZES)) if pool else None
+    up = torch.randn(len(_POOL_SIZES) if pool else 37, 1, device=cuda)
+    return [p for m in mlps for p in m.parameters()], lambda: ops.readout_mlps(
+        [_leaf(f) for f in feats], mlps, pool=pool).backward(up)
+
+
+def _case_edge_basis(cuda, mp):
+    from x2gnn import ops
+    from x2gnn.layers import RadialBasis
+
+    E, n_atoms = 37, 40
+    pos = torch.rand(n_atoms, 3, device=cuda) * 4.0
+    src = torch.randint(0, n_atoms, (E,))
+    dst = (src + torch.randint(1, n_atoms, (E,))) % n_atoms
+    lg = ops.LineGraph.__new__(ops.LineGraph)
+    lg.E, lg.edge_src, lg.edge_dst = E, src.to(torch.int32).to(cuda), dst.to(torch.int32).to(cuda)
+    rb = RadialBasis(embedding_size=6, cutoff=5.0).to(cuda)
+    up = torch.randn(E, 6, device=cuda)
+    return [rb.frequencies], lambda: ops.edge_basis(pos, lg, rb.frequencies, 5.0)[2].backward(up)
+
+
+def _case_attention(cuda, mp, fold):
+    """lin_sbf's gradients through ops.sbf_attention on the star graph with a hub of degree 70 (75 atoms): the
+    center-atom kernels with the folded source pass (x2g_sbf_radial_wgrad), and with _FOLD_SBF off the
+    two-pass backward whose T-row weight GEMM is ops.linear_wgrad."""
+    from x2gnn import ops
+
+    mp.setattr(ops, "_FOLD_SBF", fold)
+    hub = np.array([[0] * 70 + list(range(1, 71)), list(range(1, 71)) + [0] * 70])
+    hub = hub[:, np.lexsort((hub[1], hub[0]))]
+    lg = _sym_lg(hub, 75, cuda)
+    z = torch.randint(0, 10, (75,)).to(cuda)
+    lg.atom_type = ops._i32(z)
+    lg.src_type, lg.dst_type = ops._i32(z[lg.edge_src.long()]), ops._i32(z[lg.edge_dst.long()])
+    pos = torch.randn(75, 3, device=cuda)
+    sbf = ops.spherical_basis(pos, lg, torch.rand(lg.E, 42, device=cuda))
+    assert (lg.sbf_factors is not None) == fold
+    q, k, v, skip, gy = (torch.randn(lg.E, 128, device=cuda) for _ in range(5))
+    w = torch.nn.Parameter(0.2 * torch.randn(128, 42, device=cuda))
+    b = torch.nn.Parameter(0.1 * torch.randn(128, device=cuda))
+    return [w, b], lambda: ops.sbf_attention(_leaf(q), _leaf(k), _leaf(v), _leaf(skip), None, sbf, w, b, lg, 16,
+                                             8, edge_mode=ops.EDGE_NONE).backward(gy)
+
+
+def _case_embedding(cuda, mp):
+    from x2gnn import ops
+
+    w = torch.nn.Parameter(torch.randn(10, 32, device=cuda))
+    z = torch.tensor([1, 6, 6, 8, 1, 1, 7, 0, 6, 1], dtype=torch.int64, device=cuda)
+    gt = torch.randn(10, 32, device=cuda)
+    return [w], lambda: ops.embedding_table(w, z, None, 0, True).backward(gt)
+
+
+_DEST_CASES = {
+    "dense-1x6x128": (_case_dense, 1, 6, 128), "dense-70x130x20": (_case_dense, 70, 130, 20),
+    "residual_layer": (_case_residual,), "row_chain-17": (_case_row_chain, 17), "row_chain-37": (_case_row_chain, 37),
+    "table_chain": (_case_table_chain,), "featurize": (_case_featurize,),
+    "conv_projections-fused": (_case_conv_proj, 128), "conv_projections-gate": (_case_conv_proj, 64),
+    "rbf_pool": (_case_rbf_pool, 0), "rbf_pool_batch": (_case_rbf_pool, 2),
+    "readout-chain": (_case_readout, 128, False), "readout-chain-pool": (_case_readout, 128, True),
+    "readout-dense": (_case_readout, 64, False), "readout-dense-pool": (_case_readout, 64, True),
+    "edge_basis": (_case_edge_basis,), "attention-center": (_case_attention, True),
+    "attention-two-pass": (_case_attention, False), "embedding_table": (_case_embedding,),
+}
+# the weight-gradient entry a case must reach (the form of the op it is about)
+_DEST_ENTRY = {"attention-center": "x2g_sbf_radial_wgrad", "attention-two-pass": "x2g_linear_wgrad_ex",
+               "conv_projections-fused": "x2g_conv_proj_bwd_gate", "conv_projections-gate": "x2g_rbf_gate_bwd",
+               "readout-dense": "x2g_dense_bwd_batched", "readout-chain-pool": "x2g_readout_head_pool_bwd"}
+
+
+@pytest.mark.parametrize("case", sorted(_DEST_CASES))
+def test_wgrad_destination_modes(cuda, monkeypatch, case):
+    """Every backward that produces a weight gradient, from the same inputs three times: (a) plain parameters
+    (the Function returns the gradients), (b) GradBucket-backed (summed into the bucket, None returned), (c)
+    GradBucket-backed inside ops.deferred_wgrad() with the bucket prefilled with 0.5 (the slab sums and the flat
+    launch run at the context's exit and ADD).  (b) = (a) and (c) - 0.5 = (a) within rtol 1e-5 and 1e-6 of the
+    largest plain gradient (test_bucket_gradients_equal_autograd's bound: the deferred flat launch splits rows
+    differently); a parameter's hook fires exactly when the Function returned a gradient for it."""
+    from test_gpu_model import record_calls
+
+    from x2gnn import ops
+    from x2gnn.dist import GradBucket
+
+    torch.manual_seed(7)
+    build, *args = _DEST_CASES[case]
+    params, run = build(cuda, monkeypatch, *args)
+    hits = []
+    for i, p in enumerate(params):
+        p.register_hook(lambda g, i=i: hits.append(i) if g is not None else None)  # (None: nothing returned)
+    run()
+    assert sorted(hits) == list(range(len(params)))  # (a): every gradient returned, once
+    plain = [p.grad.detach().clone() for p in params]
+    top = max(float(g.abs().max()) for g in plain)
+    tol = dict(rtol=1e-5, atol=1e-6 * top)
+    bucket = GradBucket(params)
+    bucket.zero()
+    hits.clear()
+    seen = record_calls(monkeypatch)
+    run()
+    assert not hits  # (b): None for every bucket-backed parameter
+    for p, g in zip(params, plain):
+        torch.testing.assert_close(p.grad, g, **tol)
+    flags_b = _wgrad_flags(seen)
+    bucket.flat.fill_(0.5)
+    del seen[:]
+    with ops.deferred_wgrad() as d:
+        run()
+        assert d.jobs or d.tiled or case in ("table_chain", "embedding_table")  # (no slabs: summed in the launch)
+    assert not hits
+    for p, g in zip(params, plain):
+        torch.testing.assert_close(p.grad - 0.5, g, **tol)
+    # the launches took the flag word of their mode (the embedding's has no slabs to defer, the table chain's
+    # stages carry their own accumulate field), and the attention cases ran the backward they are meant for
+    flags_c = _wgrad_flags(seen)
+    both = ops.ACCUM_WGRAD if case == "embedding_table" else ops.ACCUM_WGRAD | ops.DEFER_SLAB_SUM
+    assert {f & 3 for _, f in flags_b} == ({ops.ACCUM_WGRAD} if case != "table_chain" else set()), flags_b
+    assert {f & 3 for _, f in flags_c} == ({both} if case != "table_chain" else set()), flags_c
+    assert _DEST_ENTRY.get(case) in [None] + [n for n, _ in flags_c]
+    assert case != "attention-center" or "x2g_sbf_attention_bwd_center" in [n for n, _ in seen]
+
+
+def _mixed_dense(cuda):
+    params, run = _case_dense(cuda, None, 70, 130, 20)
+    return params, run, params[:1], ["x2g_dense_bwd_ex"]
+
+
+def _mixed_readout(cuda, D):
+    params, run = _case_readout(cuda, None, D, False)
+    # the head (and at D = 64 the batched dense layers) are launches over both MLPs: all their flags 0; the
+    # D = 128 chain form's hidden layers are one flat launch per MLP, the bucketed MLP's summing into the bucket
+    return params, run, params[:6], ["x2g_readout_head_bwd"] + (["x2g_dense_bwd_batched"] if D == 64 else [])
+
+
+def _mixed_pool_batch(cuda):
+    params, run = _case_rbf_pool(cuda, None, 2)
+    return params, run, params[:2], ["x2g_rbf_gate_bwd_batch"]
+
+
+@pytest.mark.parametrize("case", ["dense", "readout-dense", "readout-chain", "rbf_pool_batch"])
+def test_wgrad_mixed_sinks_take_fresh_buffers(cuda, monkeypatch, case):
+    """A launch whose parameters are only partly bucket-backed (dense: the weight but not the bias; readout_mlps
+    and rbf_pool_batch: one of the two MLPs / jobs) raises nothing, sums nothing into the bucket itself (flag
+    word 0: fresh buffers returned for the whole launch, autograd adds them) and gives the plain gradients."""
+    from test_gpu_model import record_calls
+
+    from x2gnn import ops
+    from x2gnn.dist import GradBucket
+
+    torch.manual_seed(8)
+    build, *args = {"dense": (_mixed_dense,), "readout-dense": (_mixed_readout, 64),
+                    "readout-chain": (_mixed_readout, 128), "rbf_pool_batch": (_mixed_pool_batch,)}[case]
+    params, run, backed, entries = build(cuda, *args)
+    run()
+    plain = [p.grad.detach().clone() for p in params]
+    top = max(float(g.abs().max()) for g in plain)
+    for p in params:
+        p.grad = None
+    bucket = GradBucket(backed)
+    bucket.zero()
+    seen = record_calls(monkeypatch)
+    with ops.deferred_wgrad() as d:
+        run()
+    flags = _wgrad_flags(seen, *entries)
+    assert sorted({n for n, _ in flags}) == sorted(entries) and all(f == 0 for _, f in flags), flags
+    if case == "readout-chain":
+        assert [f for _, f in _wgrad_flags(seen, "x2g_tiled_wgrad_flat")] == [0]  # (the plain MLP's; the other queued)
+    else:
+        assert not d.jobs and not d.flat_launches
+    for p, g in zip(params, plain):
+        torch.testing.assert_close(p.grad, g, rtol=1e-5, atol=1e-6 * top)
+
+
+@pytest.mark.parametrize("case", ["dense", "linear_wgrad", "rbf_pool", "sbf_radial_wgrad"])
+def test_wgrad_zero_rows_inside_deferral(cuda, monkeypatch, case):
+    """Zero rows, bucket-backed, inside ops.deferred_wgrad(): the call returns, the entry is handed
+    X2G_ACCUM_WGRAD without X2G_DEFER_SLAB_SUM (the C entries refuse that flag at zero rows), nothing is
+    queued and the bucket keeps its prefill bit for bit."""
+    from test_gpu_model import record_calls
+
+    from x2gnn import ops
+    from x2gnn.dist import GradBucket
+
+    f = dict(device=cuda)
+    if case == "rbf_pool":
+        lin = torch.nn.Linear(6, 128).to(cuda)
+        entry = "x2g_rbf_gate_bwd"
+    elif case == "sbf_radial_wgrad":
+        lin = torch.nn.Linear(42, 128).to(cuda)
+        entry = "x2g_sbf_radial_wgrad"
+    else:
+        lin = torch.nn.Linear(6, 128).to(cuda)
+        entry = "x2g_dense_bwd_ex" if case == "dense" else "x2g_linear_wgrad_ex"
+    bucket = GradBucket(lin.parameters())
+    bucket.flat.fill_(0.5)
+    seen = record_calls(monkeypatch)
+    with ops.deferred_wgrad() as d:
+        if case == "dense":
+            ops.dense(torch.zeros(0, 6, requires_grad=True, **f), lin.weight, lin.bias).sum().backward()
+        elif case == "linear_wgrad":
+            got = ops.linear_wgrad(torch.zeros(0, 128, **f), torch.zeros(0, 6, **f), w_param=lin.weight,
+                                   b_param=lin.bias)
+            assert list(got) == [None, None]
+        elif case == "rbf_pool":
+            z = torch.zeros(1, dtype=torch.int32, **f)  # (no rows and no segments: the forward reads no pointer)
+            ops.rbf_pool(torch.zeros(0, 128, requires_grad=True, **f), torch.zeros(0, 6, **f), lin.weight, lin.bias,
+                         z[:0], z, 0).sum().backward()
+        else:
+            got = ops.sbf_radial_wgrad(torch.zeros(0, 8, 128, **f), torch.zeros(0, 42, **f), lin.weight, lin.bias)
+            assert list(got) == [None, None]
+        assert not d.jobs and not d.tiled
+    torch.cuda.synchronize()
+    assert not d.jobs and "x2g_slab_sum_batch" not in [n for n, _ in seen]
+    assert [f for _, f in _wgrad_flags(seen, entry)] == [ops.ACCUM_WGRAD]
+    assert torch.equal(bucket.flat, torch.full_like(bucket.flat, 0.5))
+
+
+def test_model_backward_one_slab_sum_one_flat_launch(cuda, monkeypatch):
+    """model_full.npz, GradBucket, backward inside ops.deferred_wgrad(): every weight-gradient entry is handed
+    X2G_ACCUM_WGRAD | X2G_DEFER_SLAB_SUM, the T-layout ones run as ONE x2g_tiled_wgrad_flat_rows launch and
+    every slab is summed by ONE x2g_slab_sum_batch launch over exactly the deferral's jobs."""
+    from helpers import batch_from_fixture
+    from test_gpu_model import product_model, record_calls
+
+    from x2gnn import ops
+    from x2gnn.dist import GradBucket
+
+    z = golden("model_full.npz")
+    b = batch_from_fixture(z).to(cuda)
+    m = product_model(z, cuda)
+    bucket = GradBucket(m.parameters())
+    bucket.zero()
+    loss = torch.nn.functional.smooth_l1_loss(m(b), b.y)
+    seen = record_calls(monkeypatch)
+    with ops.deferred_wgrad() as d:
+        loss.backward()
+    names = [n for n, _ in seen]
+    assert names.count("x2g_slab_sum_batch") == 1 and names.count("x2g_tiled_wgrad_flat_rows") == 1
+    assert "x2g_tiled_wgrad_flat" not in names
+    both = ops.ACCUM_WGRAD | ops.DEFER_SLAB_SUM
+    flags = _wgrad_flags(seen)
+    assert len(flags) > 10
+    for n, f in flags:
+        assert f & 3 == (ops.ACCUM_WGRAD if n == "x2g_embedding_table_bwd" else both), (n, f)  # (no slabs there)
+    n_jobs = [a[1] for n, a in seen if n == "x2g_slab_sum_batch"][0]
+    assert len(d.jobs) == n_jobs > 0

@@ -258,17 +258,14 @@ class _EdgeBasis(torch.autograd.Function):
         dist, env, freq = ctx.saved_tensors
         E, R = dist.shape[0], freq.shape[0]
         lib = _lib.load()
-        sink = grad_sink(ctx.freq_param)
-        dfreq = sink if sink is not None else torch.empty(R, dtype=torch.float32, device=dist.device)
+        dest = _WGradDest([ctx.freq_param], dist.device)
+        (dfreq,) = dest.bufs
         ws_bytes = int(lib.x2g_edge_basis_freq_grad_workspace(E, R))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dist.device)
-        defer = sink is not None and _defer() is not None and E > 0
-        flags = (ACCUM_WGRAD if sink is not None else 0) | (DEFER_SLAB_SUM if defer else 0)
         call("x2g_edge_basis_freq_grad", ptr(_f32(grbf)), ptr(dist), ptr(env), ptr(freq), E, R, ctx.cutoff, ptr(dfreq),
-             flags, ptr(ws), ws_bytes, stream_ptr())
-        if defer:
-            _defer_job(ws, 0, int(lib.x2g_edge_basis_freq_grad_splits(E)), R, 0, dfreq, None)
-        return (None if sink is not None else dfreq), None, None, None, None, None
+             dest.flags(E), ptr(dest.workspace(ws_bytes)), ws_bytes, stream_ptr())
+        if dest.deferral:
+            dest.queue((0, int(lib.x2g_edge_basis_freq_grad_splits(E)), R, 0, dfreq, None))
+        return (*dest.grads(), None, None, None, None, None)
 
 
 def edge_basis(pos, lg: LineGraph, freq, cutoff: float = 5.0, num_spherical: int = 7, num_radial: int = 6):
@@ -617,12 +614,9 @@ class _SBFAttention(torch.autograd.Function):
         elif mode == EDGE_PER_DST and ctx.edge_row is not None:
             # rows of the edge table are shared by many destinations: sum d_edge per table row
             d_edge = keyed_row_sum(d_edge, ctx.edge_row, ctx.edge_shape[0])
-        gw, gb = grad_sink(ctx.w_param), grad_sink(ctx.b_param)
         materialize_sbf(lg, sbf)
-        if gw is not None and gb is not None:
-            dw, db = linear_wgrad(dproj, sbf, dw_out=gw, db_out=gb)  # summed into the bucket: None
-        else:
-            dw, db = linear_wgrad(dproj, sbf)
+        # lin_sbf's dW / db (None where summed into the gradient bucket)
+        dw, db = linear_wgrad(dproj, sbf, w_param=ctx.w_param, b_param=ctx.b_param)
         return dq, dk, dv, dout, d_edge, None, dw, db, None, None, None, None, None, None
 
     @staticmethod
@@ -642,70 +636,53 @@ class _SBFAttention(torch.autograd.Function):
             # one launch for both passes, per center atom (csrc/attention_center.hip); the edge term's
             # gradient comes per center atom and is summed by the atoms' elements
             want_edge = mode == EDGE_PER_DST and ctx.needs_input_grad[4]
-            d_edge_atom = torch.empty(lg.N, D, dtype=torch.float32, device=dev) if want_edge else None
+            d_edge = torch.empty(lg.N, D, dtype=torch.float32, device=dev) if want_edge else None
             g_work = torch.empty(2, T, heads, dtype=torch.float32, device=dev)
             call("x2g_sbf_attention_bwd_center", ptr(q), ptr(k), ptr(v), ptr(edge), ptr(src_row), mode, ptr(sproj),
                  ptr(sbf_p), ptr(b_sbf), ptr(ylm), ptr(lg.atom_rowptr), ptr(lg.edge_rev), ptr(lg.rev_trip), ptr(lg.center_order),
                  ptr(alpha), ptr(smax), ptr(sden), ptr(dout), lg.N, lg.max_degree, E, T, heads, channels, ptr(dq),
-                 ptr(dk), ptr(dv), ptr(gfold), ptr(d_edge_atom), ptr(g_work), st)
-            d_edge = None
-            if want_edge:
-                if ctx.defer_edge:
-                    d_edge = keyed_row_sum_deferred(d_edge_atom, lg.atom_type, ctx.edge_shape[0], ctx.keyed_pending)
-                else:
-                    d_edge = keyed_row_sum(d_edge_atom, lg.atom_type, ctx.edge_shape[0])
-            gw, gb = grad_sink(ctx.w_param), grad_sink(ctx.b_param)
-            if gw is not None and gb is not None:
-                dw, db = sbf_radial_wgrad(gfold, radial, dw_out=gw, db_out=gb)
-            else:
-                dw, db = sbf_radial_wgrad(gfold, radial)
-            return dq, dk, dv, dout, d_edge, None, dw, db, None, None, None, None, None, None
-        d_edge = torch.empty(E, D, dtype=torch.float32, device=dev) if mode == EDGE_PER_DST else None
-        call("x2g_sbf_attention_bwd_dst_g", ptr(q), ptr(k), ptr(v), ptr(edge), ptr(ctx.edge_row), mode, ptr(sproj),
-             ptr(lg.trip_rowptr), ptr(lg.trip_src), ptr(alpha), ptr(smax), ptr(sden), ptr(dout), E, T, heads, channels,
-             ptr(dq), ptr(d_edge), ptr(g), ptr(prob), ptr(rho), st)
-        src_rowptr, src_perm = lg.src_csr()
-        rows = 0 if edge is None else edge.shape[0]
-        # the edge row per SOURCE (constant over a source segment) when the rows are the line graph's
-        # own destination elements
-        src_row = lg.src_type if (ctx.edge_row is not None and ctx.edge_row is lg.dst_type) else None
-        call("x2g_sbf_attention_bwd_src_fold", ptr(q), ptr(v), ptr(edge), ptr(ctx.edge_row), ptr(src_row), rows, mode,
-             ptr(sproj), ptr(ylm), ptr(src_rowptr), ptr(src_perm), ptr(lg.src_dst), ptr(lg.trip_dst), ptr(prob),
-             ptr(g), ptr(rho), ptr(dout), E, T, heads, channels, ptr(dk), ptr(dv), ptr(gfold), st)
-        if not ctx.needs_input_grad[4]:
-            d_edge = None  # (written by the kernel; no consumer: the table's gradient is not wanted)
-        elif mode == EDGE_PER_DST and ctx.edge_row is not None:
-            if ctx.defer_edge:
-                d_edge = keyed_row_sum_deferred(d_edge, ctx.edge_row, ctx.edge_shape[0], ctx.keyed_pending)
-            else:
-                d_edge = keyed_row_sum(d_edge, ctx.edge_row, ctx.edge_shape[0])
-        gw, gb = grad_sink(ctx.w_param), grad_sink(ctx.b_param)
-        if gw is not None and gb is not None:
-            dw, db = sbf_radial_wgrad(gfold, radial, dw_out=gw, db_out=gb)
+                 ptr(dk), ptr(dv), ptr(gfold), ptr(d_edge), ptr(g_work), st)
+            key = lg.atom_type  # d_edge per center atom: summed by the atoms' elements
         else:
-            dw, db = sbf_radial_wgrad(gfold, radial)
+            d_edge = torch.empty(E, D, dtype=torch.float32, device=dev) if mode == EDGE_PER_DST else None
+            call("x2g_sbf_attention_bwd_dst_g", ptr(q), ptr(k), ptr(v), ptr(edge), ptr(ctx.edge_row), mode, ptr(sproj),
+                 ptr(lg.trip_rowptr), ptr(lg.trip_src), ptr(alpha), ptr(smax), ptr(sden), ptr(dout), E, T, heads,
+                 channels, ptr(dq), ptr(d_edge), ptr(g), ptr(prob), ptr(rho), st)
+            src_rowptr, src_perm = lg.src_csr()
+            rows = 0 if edge is None else edge.shape[0]
+            # the edge row per SOURCE (constant over a source segment) when the rows are the line graph's
+            # own destination elements
+            src_row = lg.src_type if (ctx.edge_row is not None and ctx.edge_row is lg.dst_type) else None
+            call("x2g_sbf_attention_bwd_src_fold", ptr(q), ptr(v), ptr(edge), ptr(ctx.edge_row), ptr(src_row), rows,
+                 mode, ptr(sproj), ptr(ylm), ptr(src_rowptr), ptr(src_perm), ptr(lg.src_dst), ptr(lg.trip_dst),
+                 ptr(prob), ptr(g), ptr(rho), ptr(dout), E, T, heads, channels, ptr(dk), ptr(dv), ptr(gfold), st)
+            if not ctx.needs_input_grad[4]:
+                d_edge = None  # (written by the kernel; no consumer: the table's gradient is not wanted)
+            key = ctx.edge_row  # d_edge per destination: summed by the destinations' table rows, if it has them
+        if d_edge is not None and key is not None:
+            if ctx.defer_edge:
+                d_edge = keyed_row_sum_deferred(d_edge, key, ctx.edge_shape[0], ctx.keyed_pending)
+            else:
+                d_edge = keyed_row_sum(d_edge, key, ctx.edge_shape[0])
+        # lin_sbf's dW / db (None where summed into the gradient bucket)
+        dw, db = sbf_radial_wgrad(gfold, radial, ctx.w_param, ctx.b_param)
         return dq, dk, dv, dout, d_edge, None, dw, db, None, None, None, None, None, None
 
 
-def sbf_radial_wgrad(gfold, radial, dw_out=None, db_out=None):
+def sbf_radial_wgrad(gfold, radial, w_param=None, b_param=None):
     """(dW_sbf [D, 42], db_sbf [D]) from the source-folded gradient G [E, 8, D] and the radial
-    factor rbf_env [E, 42] (x2g_sbf_radial_wgrad); accumulates into dw_out/db_out when given."""
+    factor rbf_env [E, 42] (x2g_sbf_radial_wgrad); (None, None) when lin_sbf's parameters are given and
+    bucket-backed: summed into the bucket (_WGradDest)."""
     E, _, D = gfold.shape
-    accum = dw_out is not None
-    if accum and db_out is None:
-        raise ValueError("accumulating dW_sbf needs the bias-gradient buffer too")
-    dw = dw_out if accum else torch.empty(D, 42, dtype=torch.float32, device=gfold.device)
-    db = db_out if accum else torch.empty(D, dtype=torch.float32, device=gfold.device)
+    dest = _WGradDest([w_param, b_param], gfold.device, shapes=[(D, 42), (D,)])
+    dw, db = dest.bufs
     lib = _lib.load()
     ws_bytes = int(lib.x2g_sbf_radial_wgrad_workspace(E, D))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=gfold.device)
-    defer = accum and _defer() is not None and E > 0
-    flags = (ACCUM_WGRAD if accum else 0) | (DEFER_SLAB_SUM if defer else 0)
-    call("x2g_sbf_radial_wgrad", ptr(gfold), ptr(_f32(radial)), E, D, ptr(dw), ptr(db), flags, ptr(ws), ws_bytes,
-         stream_ptr())
-    if defer:
-        _defer_job(ws, 0, int(lib.x2g_sbf_radial_wgrad_splits(E)), D * 42, D, dw, db)
-    return (None, None) if accum else (dw, db)
+    call("x2g_sbf_radial_wgrad", ptr(gfold), ptr(_f32(radial)), E, D, ptr(dw), ptr(db), dest.flags(E),
+         ptr(dest.workspace(ws_bytes)), ws_bytes, stream_ptr())
+    if dest.deferral:
+        dest.queue((0, int(lib.x2g_sbf_radial_wgrad_splits(E)), D * 42, D, dw, db))
+    return dest.grads()
 
 
 class _EmbeddingTable(torch.autograd.Function):
@@ -730,11 +707,11 @@ class _EmbeddingTable(torch.autograd.Function):
     def backward(ctx, g):
         (counts,) = ctx.saved_tensors
         V, D = counts.shape[0], g.shape[1]
-        sink = grad_sink(ctx.w_param)
-        dw = sink if sink is not None else torch.empty(V, D, dtype=torch.float32, device=g.device)
+        dest = _WGradDest([ctx.w_param], g.device)
+        (dw,) = dest.bufs
         call("x2g_embedding_table_bwd", ptr(_f32(g)), ptr(counts) if ctx.scale else None, V, D, ctx.pad, ptr(dw),
-             ACCUM_WGRAD if sink is not None else 0, stream_ptr())
-        return (None if sink is not None else dw), None, None, None, None
+             ACCUM_WGRAD if dest.acc else 0, stream_ptr())  # (no slabs: nothing to defer)
+        return (*dest.grads(), None, None, None, None)
 
 
 def embedding_table(weight, z, max_norm, padding_idx, scale_grad_by_freq):
@@ -761,15 +738,6 @@ class HeadGroup(ctypes.Structure):
 
 def _dp(t):
     return t.data_ptr() if t is not None else None
-
-
-def _wgrad_targets(params, shapes, dev):
-    """Per parameter: (buffer, accum) — the bucket view when every one of them is bucket-backed
-    (summed straight into it), fresh buffers otherwise; returns (buffers, accum)."""
-    sinks = [grad_sink(p) for p in params]
-    if all(s is not None for s in sinks):
-        return sinks, True
-    return [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes], False
 
 
 class _ReadoutMLPs(torch.autograd.Function):
@@ -846,23 +814,22 @@ class _ReadoutMLPs(torch.autograd.Function):
         dout = _f32(dout.reshape(-1))
         # head: dh2_g = dout w3_g; dW3_g, db3_g
         dh2 = [torch.empty(R, D, **f32) for _ in range(G)]
-        (dw3, db3), acc3 = _wgrad_pairs(W3, B3, dev)
+        dest3 = _WGradDest(list(W3) + list(B3), dev)
+        dw3, db3 = dest3.bufs[:G], dest3.bufs[G:]
+        g3 = dest3.grads()
         heads = (HeadGroup * G)(*[HeadGroup(_dp(h2[g]), _dp(W3[g]), None, _dp(dh2[g]), _dp(dw3[g]), _dp(db3[g]))
                                   for g in range(G)])
         ws_bytes = int(lib.x2g_readout_head_bwd_workspace(R, D, G))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        defer = acc3 and _defer() is not None
-        hflags = (ACCUM_WGRAD if acc3 else 0) | (DEFER_SLAB_SUM if defer else 0)
+        hflags, ws = dest3.flags(R), dest3.workspace(ws_bytes)
         if ctx.pool is not None:  # dout per molecule, broadcast to its rows inside the head kernel
             seg_rowptr, n_seg = ctx.pool
             call("x2g_readout_head_pool_bwd", ptr(dout), ptr(seg_rowptr), n_seg, heads, G, R, D, hflags, ptr(ws),
                  ws_bytes, st)
         else:
             call("x2g_readout_head_bwd", ptr(dout), heads, G, R, D, hflags, ptr(ws), ws_bytes, st)
-        if defer:
+        if dest3.deferral:  # readout g's slabs: splits x (D weights + 1 bias) floats, one readout after another
             splits = int(lib.x2g_readout_head_bwd_splits(R))
-            for g in range(G):
-                _defer_job(ws, g * splits * (D + 1) * 4, splits, D, 1, dw3[g], db3[g])
+            dest3.queue(*[(g * splits * (D + 1) * 4, splits, D, 1, dw3[g], db3[g]) for g in range(G)])
         if ctx.chain:  # both hidden layers' data gradients in one launch; dW / db from the T layout
             dfeat = [torch.empty(R, D, **f32) for _ in range(G)]
             dz_t = torch.empty_like(in_t)
@@ -876,34 +843,29 @@ class _ReadoutMLPs(torch.autograd.Function):
             for g in range(G):
                 dws, dbs = chain_wgrad(in_t[g], dz_t[g], R, [W1[g], W2[g]], [B1[g], B2[g]],
                                        x0=saved[3 * G + 2 + g] if ctx.rm0 else None)
-                pg += [dws[0], dbs[0], dws[1], dbs[1]]
-                pg += [None if acc3 else dw3[g].view_as(W3[g]), None if acc3 else db3[g]]
+                pg += [dws[0], dbs[0], dws[1], dbs[1], g3[g], g3[G + g]]
             return (None, None, *dfeat, *pg)
         grads = {}
         # layer 2 then layer 1: dz = dy * SiLU'(z), dx = dz W, dW / db
         dy = dh2
         for (layer, x_in, z, W, B) in ((2, h1, z2, W2, B2), (1, xs, z1, W1, B1)):
             dx = [torch.empty(R, D, **f32) for _ in range(G)]
-            (dw, db), acc = _wgrad_pairs(W, B, dev)
+            dest = _WGradDest(list(W) + list(B), dev)
+            dw, db = dest.bufs[:G], dest.bufs[G:]
             grp = (DenseBwdGroup * G)(*[DenseBwdGroup(_dp(dy[g]), _dp(z[g]), _dp(x_in[g]), _dp(W[g]), _dp(dx[g]), None,
                                                       _dp(dw[g]), _dp(db[g])) for g in range(G)])
             wsz = int(lib.x2g_dense_bwd_workspace(R, D, D))
-            ws = torch.empty(max(wsz * G, 1), dtype=torch.uint8, device=dev)
-            defer = acc and _defer() is not None
-            call("x2g_dense_bwd_batched", grp, G, R, D, D, ACT_SILU, (ACCUM_WGRAD if acc else 0) |
-                 (DEFER_SLAB_SUM if defer else 0), ptr(ws), wsz * G, st)
-            if defer:
+            call("x2g_dense_bwd_batched", grp, G, R, D, D, ACT_SILU, dest.flags(R), ptr(dest.workspace(wsz * G)),
+                 wsz * G, st)
+            if dest.deferral:  # readout g's slabs lead its own x2g_dense_bwd_workspace share
                 splits = int(lib.x2g_dense_bwd_splits(R, D, D))
-                for g in range(G):
-                    _defer_job(ws, g * wsz, splits, D * D, D, dw[g], db[g])
-            grads[layer] = (None, None) if acc else (dw, db)
+                dest.queue(*[(g * wsz, splits, D * D, D, dw[g], db[g]) for g in range(G)])
+            grads[layer] = dest.grads()
             dy = dx
         dfeat = dy
         pg = []
         for g in range(G):
-            for (dw, db) in (grads[1], grads[2]):
-                pg += [None if dw is None else dw[g], None if db is None else db[g]]
-            pg += [None if acc3 else dw3[g].view_as(W3[g]), None if acc3 else db3[g]]
+            pg += [grads[1][g], grads[1][G + g], grads[2][g], grads[2][G + g], g3[g], g3[G + g]]
         return (None, None, *dfeat, *pg)
 
 
@@ -945,15 +907,6 @@ def _readout_chain_ok(R, D, G, *weights):
             if w is not None and (w.dtype != torch.float32 or not w.is_contiguous() or w.data_ptr() % 16):
                 return False
     return all(tuple(w.shape) == (128, 128) for ws in (weights[0], weights[2]) for w in ws)
-
-
-def _wgrad_pairs(Ws, Bs, dev):
-    """Weight / bias gradient buffers of a group of layers: the bucket views (accumulate) when all
-    are bucket-backed, fresh buffers otherwise."""
-    params = list(Ws) + list(Bs)
-    bufs, acc = _wgrad_targets(params, [tuple(p.shape) for p in params], dev)
-    n = len(Ws)
-    return (bufs[:n], bufs[n:]), acc
 
 
 def readout_mlps_supported(feats, mlps):
@@ -1305,19 +1258,6 @@ def deferred_wgrad():
             _DEFERRALS[key] = prev
 
 
-def _defer_job(ws, offset, splits, n_w, n_b, dw, db, ld=0, cols=0, dw_ptr=None, db_ptr=None, d=None):
-    """Queue one slab reduction (x2g_slab_job) on the open deferral; dw_ptr / db_ptr: raw
-    destinations (a block of a larger weight) instead of the tensors' own pointers."""
-    d = d if d is not None else _defer()
-    base = ws.data_ptr() + int(offset)
-    has_b = db is not None or db_ptr is not None
-    part_b = base + 4 * splits * n_w if has_b else None
-    d.jobs.append(SlabJob(base, part_b, dw_ptr if dw_ptr is not None else dw.data_ptr(),
-                          (db_ptr if db_ptr is not None else db.data_ptr()) if has_b else None, n_w,
-                          n_b if has_b else 0, splits, ld, cols))
-    d.keep.append(ws)
-
-
 _APPLY_GRAD = [True]  # the caller's grad mode at the innermost Function.apply in flight (_apply)
 
 
@@ -1354,6 +1294,53 @@ def grad_sink(param):
     if g is None or not g.is_contiguous() or g.dtype != torch.float32:
         return None
     return g
+
+
+class _WGradDest:
+    """Where the weight gradients of ONE launch go, and when their partial slabs are summed.
+
+    ``params``: the launch's parameters, None for an absent bias (``shapes``: their shapes, for a caller
+    that may have no parameter objects).  ``bufs`` holds per parameter the gradient-bucket view
+    (``grad_sink``) when every present one is bucket-backed — the kernel then sums into the bucket
+    (``acc``) and ``grads()``, what the Function returns for them, is all None — and otherwise a fresh
+    fp32 buffer each, which ``grads()`` returns.  ``flags(rows)`` is the entry's flag word and
+    ``workspace(n)`` its workspace; inside ``deferred_wgrad()`` the flag word leaves the slab sum to the
+    context's one batched launch (``deferral`` is then set) and ``queue`` hands it the slabs."""
+
+    def __init__(self, params, dev, shapes=None):
+        if shapes is None:
+            shapes = [None if p is None else p.shape for p in params]
+        sinks = [None if sh is None else grad_sink(p) for p, sh in zip(params, shapes)]
+        self.acc = all(s is not None for s, sh in zip(sinks, shapes) if sh is not None)
+        self.bufs = sinks if self.acc else [None if sh is None else torch.empty(tuple(sh), dtype=torch.float32,
+                                                                               device=dev) for sh in shapes]
+        self.dev, self.deferral, self.ws = dev, None, None
+
+    def flags(self, rows):
+        """X2G_ACCUM_WGRAD when summing into the bucket, and with it X2G_DEFER_SLAB_SUM when a deferral is
+        open on this stream and the launch has rows (the C entries refuse the flag at zero rows)."""
+        self.deferral = _defer() if self.acc and rows > 0 else None
+        return (ACCUM_WGRAD if self.acc else 0) | (DEFER_SLAB_SUM if self.deferral is not None else 0)
+
+    def workspace(self, n, least=1):
+        self.ws = torch.empty(max(int(n), least), dtype=torch.uint8, device=self.dev)
+        return self.ws
+
+    def queue(self, *slabs, jobs=()):
+        """Queue the slab sums on the deferral, which keeps the workspace alive until they ran: per
+        destination (byte offset in the workspace, splits, n_w, n_b, dw, db or None) — ``splits`` slabs of
+        n_w weight floats, then ``splits`` of n_b bias floats — or the ``jobs`` (SlabJob array) an entry
+        reported itself."""
+        d = self.deferral
+        for offset, splits, n_w, n_b, dw, db in slabs:
+            base = self.ws.data_ptr() + int(offset)
+            d.jobs.append(SlabJob(base, None if db is None else base + 4 * splits * n_w, dw.data_ptr(), _dp(db), n_w,
+                                  0 if db is None else n_b, splits, 0, 0))
+        d.jobs.extend(jobs)
+        d.keep.append(self.ws)
+
+    def grads(self):
+        return [None] * len(self.bufs) if self.acc else self.bufs
 
 
 class FanIn:
@@ -1394,26 +1381,22 @@ def _fan_of(t):
     return f.register() if f is not None else None
 
 
-def linear_wgrad(dy, x, bias=True, dw_out=None, db_out=None):
+def linear_wgrad(dy, x, bias=True, w_param=None, b_param=None):
     """(dW [O, I], db [O] or None) with dW = dy^T x, db = column sums of dy, for row-major
-    dy [R, O], x [R, I]: row-split MFMA partials + fixed-order slab sum (csrc/linear.hip)."""
+    dy [R, O], x [R, I]: row-split MFMA partials + fixed-order slab sum (csrc/linear.hip).  With the
+    layer's parameters given and bucket-backed: summed into the bucket, (None, None) (_WGradDest)."""
     _need_cuda(dy, x)
     dy, x = _f32(dy), _f32(x)
     R, O = dy.shape
     I = x.shape[1]
-    accum = dw_out is not None
-    if accum and bias and db_out is None:
-        raise ValueError("accumulating dW needs the bias-gradient buffer too")
-    dw = dw_out if accum else torch.empty(O, I, dtype=torch.float32, device=dy.device)
-    db = (db_out if accum else torch.empty(O, dtype=torch.float32, device=dy.device)) if bias else None
+    dest = _WGradDest([w_param, b_param], dy.device, shapes=[(O, I), (O,) if bias else None])
+    dw, db = dest.bufs
     ws_bytes = int(_lib.load().x2g_linear_wgrad_workspace(R, O, I))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dy.device)
-    defer = accum and _defer() is not None and R > 0
-    flags = (ACCUM_WGRAD if accum else 0) | (DEFER_SLAB_SUM if defer else 0)
-    call("x2g_linear_wgrad_ex", ptr(dy), ptr(x), R, O, I, ptr(dw), ptr(db), flags, ptr(ws), ws_bytes, stream_ptr())
-    if defer:
-        _defer_job(ws, 0, int(_lib.load().x2g_linear_wgrad_splits(R, O, I)), O * I, O, dw, db)
-    return (None, None) if accum else (dw, db)
+    call("x2g_linear_wgrad_ex", ptr(dy), ptr(x), R, O, I, ptr(dw), ptr(db), dest.flags(R),
+         ptr(dest.workspace(ws_bytes)), ws_bytes, stream_ptr())
+    if dest.deferral:
+        dest.queue((0, int(_lib.load().x2g_linear_wgrad_splits(R, O, I)), O * I, O, dw, db))
+    return dest.grads()
 
 
 ACT_NONE, ACT_SILU = 0, 1
@@ -1441,27 +1424,15 @@ def _dense_bwd_raw(gy2, z, act, x2, w, w_param, b_param, has_bias, need_dx, dx_a
     dx = None
     if need_dx or dx_add is not None:  # (the kernels form dz = dy * act'(z) themselves when dx is not wanted)
         dx = dx_out if dx_out is not None else torch.empty(R, K, dtype=torch.float32, device=dev)
-    gw = grad_sink(w_param)
-    gb = grad_sink(b_param) if has_bias else None
-    accum = gw is not None and (gb is not None or not has_bias)
-    if accum:
-        dw, db = gw, gb
-    else:
-        dw = torch.empty(N, K, dtype=torch.float32, device=dev)
-        db = torch.empty(N, dtype=torch.float32, device=dev) if has_bias else None
+    dest = _WGradDest([w_param, b_param], dev, shapes=[(N, K), (N,) if has_bias else None])
+    dw, db = dest.bufs
     lib = _lib.load()
     ws_bytes = int(lib.x2g_dense_bwd_workspace(R, K, N))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    defer = accum and _defer() is not None and R > 0
-    flags = (ACCUM_WGRAD if accum else 0) | (DEFER_SLAB_SUM if defer else 0)
     call("x2g_dense_bwd_ex", ptr(gy2), ptr(z), act, ptr(x2), ptr(w), R, K, N, ptr(dx), ptr(dx_add), ptr(dw), ptr(db),
-         flags, ptr(ws), ws_bytes, stream_ptr())
-    if defer:
-        _defer_job(ws, lib.x2g_dense_bwd_slab_offset(R, K, N), int(lib.x2g_dense_bwd_splits(R, K, N)), N * K, N, dw,
-                   db)
-    if accum:
-        return dx, None, None
-    return dx, dw, db
+         dest.flags(R), ptr(dest.workspace(ws_bytes)), ws_bytes, stream_ptr())
+    if dest.deferral:  # (the slabs follow the kernel's dz buffer)
+        dest.queue((lib.x2g_dense_bwd_slab_offset(R, K, N), int(lib.x2g_dense_bwd_splits(R, K, N)), N * K, N, dw, db))
+    return (dx, *dest.grads())
 
 
 class _DenseFn(torch.autograd.Function):
@@ -1561,19 +1532,16 @@ def chain_wgrad(in_t, dz_t, R, weights, biases, x0=None):
     ``deferred_wgrad()``.  ``x0``: the chain's input, row-major [R, D], when the forward ran with
     CHAIN_IN0_ROWMAJOR (plane 0 of ``in_t`` is then unwritten and stage 0 reads ``x0``)."""
     n = len(weights)
-    params = list(weights) + [b for b in biases if b is not None]
-    bufs, acc = _wgrad_targets(params, [tuple(p.shape) for p in params], in_t.device)
-    dws, rest = bufs[:n], iter(bufs[n:])
-    dbs = [next(rest) if b is not None else None for b in biases]
+    dest = _WGradDest(list(weights) + list(biases), in_t.device)
+    dws, dbs = dest.bufs[:n], dest.bufs[n:]
     tf = in_t.shape[1]
     jobs = [TiledJob(dz_t.data_ptr() + 4 * g * tf, in_t.data_ptr() + 4 * g * tf, _dp(dws[g]), _dp(dbs[g]), 0, 0)
             for g in range(n)]
     if x0 is not None:
         jobs[0] = TiledJob(dz_t.data_ptr(), x0.data_ptr(), _dp(dws[0]), _dp(dbs[0]), 0, 0, TILED_X_ROWMAJOR)
-    _run_tiled(R, jobs, [in_t, dz_t] + ([x0] if x0 is not None else []), acc)
-    if acc:
-        return [None] * n, [None] * n
-    return dws, dbs
+    _run_tiled(R, jobs, [in_t, dz_t] + ([x0] if x0 is not None else []), dest.acc)
+    grads = dest.grads()
+    return grads[:n], grads[n:]
 
 
 class _ChainFn(torch.autograd.Function):
@@ -1775,29 +1743,21 @@ class _TableChainFn(torch.autograd.Function):
         R, D = x2.shape
         dev = x2.device
         dys = [_f32(g).contiguous() if g is not None else None for g in gys]
-        grads, stages = [], []
+        # the kernel sums or stores per stage (x2g_table_bwd_stage.accum): one destination per stage's pair
+        dests = [_WGradDest(ctx.params[2 * s:2 * s + 2], dev) for s in range(n)]
+        stages = []
         for s in range(n):
-            wp, bp = ctx.params[2 * s], ctx.params[2 * s + 1]
-            gw = grad_sink(wp)
-            gb = grad_sink(bp) if bp is not None else None
-            accum = gw is not None and (bp is None or gb is not None)
-            if accum:
-                dw, db = gw, gb
-                grads += [None, None]
-            else:
-                dw = torch.empty(D, D, dtype=torch.float32, device=dev)
-                db = torch.empty(D, dtype=torch.float32, device=dev) if bp is not None else None
-                grads += [dw, db]
+            dw, db = dests[s].bufs
             par, act = spec[s]
             src = x2 if par < 0 else ys[par]
             stages.append(TableBwdStage(_dp(ws[s]), _dp(src), _dp(zs[s]), _dp(dys[s]), _dp(dw), _dp(db), par, act,
-                                        1 if accum else 0))
+                                        1 if dests[s].acc else 0))
         dx = torch.empty(R, D, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         # several leaves (the four lin_edge): leaf stages side by side, then the inner ones
         wsb = int(_lib.load().x2g_table_chain_bwd_workspace(n))
-        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-        call("x2g_table_chain_bwd_ex", (TableBwdStage * n)(*stages), n, R, D, ptr(dx), ptr(ws), wsb, stream_ptr())
-        return (dx, None, None, *grads)
+        call("x2g_table_chain_bwd_ex", (TableBwdStage * n)(*stages), n, R, D, ptr(dx),
+             ptr(dests[0].workspace(wsb, least=16)), wsb, stream_ptr())
+        return (dx, None, None, *(g for d in dests for g in d.grads()))
 
 
 def table_chain(x, stages):
@@ -1868,14 +1828,8 @@ class _FeaturizeFn(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         dz2_t, dz1_t = torch.empty(max(tf, 1), **f32), torch.empty(max(2 * tf, 1), **f32)
         call("x2g_feat_bwd", ptr(_f32(gy)), ptr(z2_t), ptr(z1_t), ptr(W2), R, ptr(dz2_t), ptr(dz1_t), stream_ptr())
-        w1, b1, w2, b2 = ctx.params
-        params = [p for p in (w1, b1, w2, b2) if p is not None]
-        bufs, acc = _wgrad_targets(params, [tuple(p.shape) for p in params], dev)
-        it = iter(bufs)
-        dw1 = next(it)
-        db1 = next(it) if b1 is not None else None
-        dw2 = next(it)
-        db2 = next(it) if b2 is not None else None
+        dest = _WGradDest(ctx.params, dev)
+        dw1, db1, dw2, db2 = dest.bufs
         fb = 4  # bytes per float
         specs = []  # (dy_t, x_t, dw pointer, db pointer, ld, cols)
         for o in range(2):
@@ -1887,10 +1841,8 @@ class _FeaturizeFn(torch.autograd.Function):
         for i in range(2):
             specs.append((dz2_t.data_ptr(), y1_t.data_ptr() + fb * i * tf, dw2.data_ptr() + fb * i * 128,
                           db2.data_ptr() if (db2 is not None and i == 0) else None, 256, 128))
-        _run_tiled(R, [TiledJob(*sp) for sp in specs], [dz1_t, dz2_t, xs_t, y1_t], acc)
-        if acc:
-            return None, None, None, None, None, None
-        return None, None, dw1, db1, dw2, db2
+        _run_tiled(R, [TiledJob(*sp) for sp in specs], [dz1_t, dz2_t, xs_t, y1_t], dest.acc)
+        return (None, None, *dest.grads())
 
 
 def featurize(x, env, lin1, lin2):
@@ -1949,16 +1901,13 @@ def tiled_wgrad(dy_ts, x_ts, R, weights, biases, layouts=None):
     ``layouts``: per job TILED_*_ROWMAJOR bits for operands given as row-major [R, D] tensors (default:
     all in the T layout)."""
     n = len(weights)
-    params = list(weights) + [b for b in biases if b is not None]
-    bufs, acc = _wgrad_targets(params, [tuple(p.shape) for p in params], dy_ts[0].device)
-    dws, rest = bufs[:n], iter(bufs[n:])
-    dbs = [next(rest) if b is not None else None for b in biases]
+    dest = _WGradDest(list(weights) + list(biases), dy_ts[0].device)
+    dws, dbs = dest.bufs[:n], dest.bufs[n:]
     lay = layouts if layouts is not None else [0] * n
     jobs = [TiledJob(_dp(dy_ts[g]), _dp(x_ts[g]), _dp(dws[g]), _dp(dbs[g]), 0, 0, lay[g]) for g in range(n)]
-    _run_tiled(R, jobs, list(dy_ts) + list(x_ts), acc)
-    if acc:
-        return [None] * n, [None] * n
-    return dws, dbs
+    _run_tiled(R, jobs, list(dy_ts) + list(x_ts), dest.acc)
+    grads = dest.grads()
+    return grads[:n], grads[n:]
 
 
 def conv_proj_fused_supported(x, rbf, weights, biases):
@@ -1982,20 +1931,17 @@ def _conv_proj_bwd_gate(grads, x2, rbf2, Wr, wr, dx, first_x, need_rbf, drbf_out
     dev = x2.device
     drbf = drbf_out if drbf_out is not None else (
         torch.empty(E, RR, dtype=torch.float32, device=dev) if need_rbf else None)
-    gw = grad_sink(wr)
-    accum = gw is not None
-    dw = gw if accum else torch.empty(D, RR, dtype=torch.float32, device=dev)
+    dest = _WGradDest([wr], dev, shapes=[(D, RR)])
+    (dw,) = dest.bufs
     lib = _lib.load()
     ws_bytes = int(lib.x2g_conv_proj_bwd_gate_workspace(E, RR))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    defer = accum and _defer() is not None and E > 0
-    flags = ((ACCUM_WGRAD if accum else 0) | (DEFER_SLAB_SUM if defer else 0)
-             | (GATE_DRBF_ACCUM if (need_rbf and not first_r) else 0))
+    flags = dest.flags(E) | (GATE_DRBF_ACCUM if (need_rbf and not first_r) else 0)
     call("x2g_conv_proj_bwd_gate", grads, E, D, ptr(x2), ptr(rbf2), RR, ptr(Wr), ptr(dx),
-         None if first_x else ptr(dx), ptr(drbf), ptr(dw), flags, ptr(ws), ws_bytes, stream_ptr())
-    if defer:
-        _defer_job(ws, 0, int(lib.x2g_conv_proj_bwd_gate_splits(E)), D * RR, 0, dw, None)
-    return dx, drbf, (None if accum else dw)
+         None if first_x else ptr(dx), ptr(drbf), ptr(dw), flags, ptr(dest.workspace(ws_bytes)), ws_bytes,
+         stream_ptr())
+    if dest.deferral:
+        dest.queue((0, int(lib.x2g_conv_proj_bwd_gate_splits(E)), D * RR, 0, dw, None))
+    return (dx, drbf, *dest.grads())
 
 
 class _ConvProjFusedFn(torch.autograd.Function):
@@ -2142,24 +2088,16 @@ def _gate_bwd(g, owner, x, rbf, w, b, w_param, b_param, need_dx, need_rbf, dx_ad
     dx = dx_out if dx_out is not None else (torch.empty(rows, D, dtype=torch.float32, device=dev) if need_dx else None)
     drbf = drbf_out if drbf_out is not None else (
         torch.empty(rows, R, dtype=torch.float32, device=dev) if need_rbf else None)
-    has_bias = b is not None
-    gw, gb = grad_sink(w_param), (grad_sink(b_param) if has_bias else None)
-    accum = gw is not None and (gb is not None or not has_bias)
-    if accum:
-        dw, db = gw, gb
-    else:
-        dw = torch.empty(D, R, dtype=torch.float32, device=dev)
-        db = torch.empty(D, dtype=torch.float32, device=dev) if has_bias else None
+    dest = _WGradDest([w_param, b_param], dev, shapes=[(D, R), None if b is None else (D,)])
+    dw, db = dest.bufs
     lib = _lib.load()
     ws_bytes = int(lib.x2g_rbf_gate_bwd_workspace(rows, D, R))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    defer = accum and _defer() is not None and rows > 0
-    flags = (ACCUM_WGRAD if accum else 0) | (DEFER_SLAB_SUM if defer else 0) | (GATE_DRBF_ACCUM if drbf_acc else 0)
+    flags = dest.flags(rows) | (GATE_DRBF_ACCUM if drbf_acc else 0)
     call("x2g_rbf_gate_bwd", ptr(g), ptr(owner), ptr(x), ptr(rbf), ptr(w), ptr(b), rows, D, R, ptr(dx), ptr(dx_add),
-         ptr(drbf), ptr(dw), ptr(db), flags, ptr(ws), ws_bytes, stream_ptr())
-    if defer:
-        _defer_job(ws, 0, int(lib.x2g_rbf_gate_bwd_splits(rows)), D * R, D, dw, db)
-    return dx, drbf, (None if accum else dw), (None if accum else db)
+         ptr(drbf), ptr(dw), ptr(db), flags, ptr(dest.workspace(ws_bytes)), ws_bytes, stream_ptr())
+    if dest.deferral:
+        dest.queue((0, int(lib.x2g_rbf_gate_bwd_splits(rows)), D * R, D, dw, db))
+    return (dx, drbf, *dest.grads())
 
 
 class _RbfPoolFn(torch.autograd.Function):
@@ -2251,7 +2189,9 @@ class _RbfPoolBatchFn(torch.autograd.Function):
                 drbf, first_r = ctx.fan_r.take(rbf2.shape, dev)
             else:
                 drbf = torch.empty(rows, R, dtype=torch.float32, device=dev)
-        dx_ret, jobs, keep, sinks = [], [], [], []
+        dest = _WGradDest(list(ws) + list(bs), dev)  # one launch, one flag word: all jobs sum into the bucket or none
+        dws, dbs = dest.bufs[:n], dest.bufs[n:]
+        dx_ret, jobs, keep = [], [], []
         for j in range(n):
             need_x = ctx.needs_input_grad[5 + j]
             dx, first = None, True
@@ -2261,36 +2201,19 @@ class _RbfPoolBatchFn(torch.autograd.Function):
                 else:
                     dx = torch.empty(rows, D, dtype=torch.float32, device=dev)
             dx_ret.append(dx if (need_x and first) else None)
-            has_b = ctx.B[j] is not None
-            gw, gb = grad_sink(ws[j]), (grad_sink(bs[j]) if has_b else None)
-            accum = gw is not None and (gb is not None or not has_b)
-            if not accum:
-                gw = torch.empty(D, R, dtype=torch.float32, device=dev)
-                gb = torch.empty(D, dtype=torch.float32, device=dev) if has_b else None
-            sinks.append((accum, gw, gb))
             g = _f32(gps[j]) if gps[j] is not None else torch.zeros(ctx.n_seg, D, dtype=torch.float32, device=dev)
             keep.append(g)
             jobs.append(GateJob(x2[j].data_ptr(), W[j].data_ptr(), _addr(ctx.B[j]), None, g.data_ptr(), _addr(dx),
-                                None if first else _addr(dx), gw.data_ptr(), _addr(gb)))
-        accums = {a for a, _, _ in sinks}
-        if len(accums) != 1:
-            raise RuntimeError("rbf_pool_batch: mixed bucket / plain weight gradients in one batch")
-        accum = accums.pop()
+                                None if first else _addr(dx), dws[j].data_ptr(), _addr(dbs[j])))
         lib = _lib.load()
         ws_bytes = int(lib.x2g_rbf_gate_bwd_batch_workspace(rows, D, R, n))
-        wsb = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        d = _defer() if accum else None
-        defer = d is not None
-        flags = (ACCUM_WGRAD if accum else 0) | (DEFER_SLAB_SUM if defer else 0) | (0 if first_r else GATE_DRBF_ACCUM)
-        out = (SlabJob * n)()
+        flags = dest.flags(rows) | (0 if first_r else GATE_DRBF_ACCUM)
+        out = (SlabJob * n)()  # the entry reports its slabs itself
         call("x2g_rbf_gate_bwd_batch", (GateJob * n)(*jobs), n, ptr(ctx.owner), ptr(rbf2), rows, D, R, ptr(drbf), flags,
-             out, ptr(wsb), ws_bytes, stream_ptr())
-        if defer:
-            d.jobs.extend(out)
-            d.keep.append(wsb)
-        dws = [None if accum else gw for _, gw, _ in sinks]
-        dbs = [None if accum else gb for _, _, gb in sinks]
-        return (None, drbf if (need_r and first_r) else None, None, None, None, *dx_ret, *dws, *dbs)
+             out, ptr(dest.workspace(ws_bytes)), ws_bytes, stream_ptr())
+        if dest.deferral:
+            dest.queue(jobs=out)
+        return (None, drbf if (need_r and first_r) else None, None, None, None, *dx_ret, *dest.grads())
 
 
 def rbf_pool_batch(xs, rbf, weights, biases, owner, rowptr, n_seg: int):
