@@ -222,7 +222,9 @@ int x2g_embedding_table_bwd(const float* g, const float* counts, int32_t num_emb
  *                                                       sbftransformer_conv.py:99-101)
  * pool:  out[n, :] = sum_{e in [rowptr[n], rowptr[n+1])} x[e, :] * f[e, :]
  *        (AtomWise / MolWise edge->atom pooling, readout.py:39-41,66-67; rows sorted by owner)
- * The [E, D] filter f is never materialised. */
+ * The [E, D] filter f is never materialised.  rows == 0 / num_segments == 0 (the batch form included) return
+ * X2G_OK and write nothing; an empty segment's row of out is written as zeros.  D outside 64 / 128 / 256 or R
+ * outside 1..8 is X2G_EUNSUPPORTED. */
 int x2g_rbf_gate_fwd(const float* x, const float* rbf, const float* w, const float* b, int64_t rows, int32_t D,
                      int32_t R, float* out, void* stream);
 int x2g_rbf_pool_fwd(const float* x, const float* rbf, const float* w, const float* b, const int32_t* rowptr,
@@ -233,7 +235,9 @@ int x2g_rbf_pool_fwd(const float* x, const float* rbf, const float* w, const flo
  *   (added to drbf's contents with flags X2G_GATE_DRBF_ACCUM: the rbf feeds every layer's gate),
  *   dw[c, j] (+)= sum_e (g_row x[e])_c rbf[e, j],  db[c] (+)= sum_e (g_row x[e])_c   (db optional).
  * dx / drbf may be NULL (not needed).  Weight gradients: per-workgroup partials + fixed-order
- * sum, flags as x2g_linear_wgrad_ex (slabs of D*R then D floats at the start of the workspace). */
+ * sum, flags as x2g_linear_wgrad_ex (x2g_rbf_gate_bwd_splits slabs of D*R floats at the start of the workspace,
+ * then, when db is given, as many slabs of D floats).  rows == 0: dw / db are zeroed (added to: left as they are)
+ * and nothing else is written; X2G_DEFER_SLAB_SUM is then X2G_EINVAL. */
 #define X2G_GATE_DRBF_ACCUM 4
 size_t x2g_rbf_gate_bwd_workspace(int64_t rows, int32_t D, int32_t R);
 int32_t x2g_rbf_gate_bwd_splits(int64_t rows);
@@ -739,7 +743,11 @@ int x2g_dense_bwd_batched(const x2g_dense_bwd_group* groups, int32_t num_groups,
                           int32_t in_features, int32_t out_features, int act, int flags, void* workspace,
                           size_t workspace_bytes, void* stream);
 
-/* The readouts' last Linear(D, 1) summed over groups: out[r] = sum_g (h_g[r, :] . w_g + b_g). */
+/* The readouts' last Linear(D, 1) summed over groups: out[r] = sum_g (h_g[r, :] . w_g + b_g).
+ * D in 4, 8, 16, .., 256, at most X2G_MAX_GROUPS groups, h / w / dh 16-byte aligned and h, w non-NULL (checked
+ * before the row count, at 0 rows too), else X2G_EUNSUPPORTED.  0 rows (forward) or 0 segments (pool forward)
+ * write nothing; the backward at 0 rows zeroes dw / db (X2G_ACCUM_WGRAD: leaves them), X2G_DEFER_SLAB_SUM is
+ * then X2G_EINVAL. */
 typedef struct {
   const float* h; /* [R, D] */
   const float* w; /* [D] */
