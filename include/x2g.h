@@ -588,6 +588,19 @@ int x2g_smooth_l1_mean_bwd(const float* pred, const float* target, int64_t n, fl
 int x2g_smooth_l1_mean_fwd_grad(const float* pred, const float* target, int64_t n, float beta, float* out,
                                 float* dpred_unit, void* stream);
 
+/* ---------------------------------------------------------------- evaluation metrics
+ * Error statistics of one batch ADDED to a running accumulator (trainer.py:57 without the per-batch .item()).
+ * d_i = pred[i] - target[i] formed in fp32 (as torch forms it), everything after that in fp64:
+ *   acc[0] += sum |d_i|    acc[1] += sum d_i^2    acc[2] = max(acc[2], max |d_i|)    acc[3] += n
+ * acc: 4 doubles, 8-byte aligned, owned and zeroed by the caller.  One launch, one 256-thread workgroup,
+ * fixed summation order (per-thread strided sums, wave reduction, then the waves in index order), no
+ * atomics; acc is read and written by one thread only.  Any n >= 1; n <= 0, a NULL pointer or a misaligned
+ * acc is X2G_EINVAL (checked on the host before any launch). */
+int x2g_error_accum(const float* pred, const float* target, int64_t n, double* acc, void* stream);
+/* acc[0] += weight * value[0]; acc[1] += weight   (trainer.py:45: loss.item() * num_graphs, kept on the
+ * device).  acc: 2 doubles, 8-byte aligned; a NULL pointer or a misaligned acc is X2G_EINVAL. */
+int x2g_weighted_accum(const float* value, double weight, double* acc, void* stream);
+
 /* ---------------------------------------------------------------- dense-layer gradients */
 
 /* Workspace bytes for x2g_linear_wgrad_ex (row-split partial slabs). */

@@ -11,10 +11,11 @@ from .layers import AtomWise, EmbeddingBlock, F_B_2D, MolWise, RadialBasis, Resi
 from .model import LayerNorm, SBFTransformer, SBFTransformerGlobal
 from .plan import GraphPlan
 from .sbftransformer_conv import SBFTransformerConv
+from .train import Evaluator, Inference, Trainer
 from .xgnn import xgnn_poly, xgnn_poly_global
 
 __all__ = [
-    "AtomWise", "Batch", "Data", "DeviceDataset", "EmbeddingBlock", "F_B_2D", "GraphPlan", "LayerNorm", "MolWise",
-    "RadialBasis", "ResidualLayer", "SBFTransformer", "SBFTransformerConv", "SBFTransformerGlobal", "collate", "molecule_to_data",
-    "poly_envelop", "xgnn_poly", "xgnn_poly_global",
+    "AtomWise", "Batch", "Data", "DeviceDataset", "EmbeddingBlock", "Evaluator", "F_B_2D", "GraphPlan", "Inference",
+    "LayerNorm", "MolWise", "RadialBasis", "ResidualLayer", "SBFTransformer", "SBFTransformerConv",
+    "SBFTransformerGlobal", "Trainer", "collate", "molecule_to_data", "poly_envelop", "xgnn_poly", "xgnn_poly_global",
 ]

@@ -108,6 +108,8 @@ SIGNATURES = {
     "x2g_smooth_l1_mean_fwd": [_P, _P, _I64, _F, _P, _P],
     "x2g_smooth_l1_mean_fwd_grad": [_P, _P, _I64, _F, _P, _P, _P],
     "x2g_smooth_l1_mean_bwd": [_P, _P, _I64, _F, _P, _P, _P],
+    "x2g_error_accum": [_P, _P, _I64, _P, _P],
+    "x2g_weighted_accum": [_P, ctypes.c_double, _P, _P],
     "x2g_chain_bwd_batch": [_P, _I32, _I32, _I64, _I32, _P],
     "x2g_graph_layernorm_bwd_ex": [_P, _P, _P, _P, _I64, _I64, _P, _P, _SZ, _P],
     "x2g_graph_layernorm_bwd_rows": [_P, _P, _P, _P, _I64, _I64, _P, _P, _P],

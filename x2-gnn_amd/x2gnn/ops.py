@@ -2528,3 +2528,36 @@ def smooth_l1_loss(pred, target, beta: float = 1.0, unit_seed=None):
             or beta <= 0):  # beta <= 0 is torch's L1 branch, not compiled
         return torch.nn.functional.smooth_l1_loss(pred, target, beta=beta)
     return _SmoothL1MeanFn.apply(pred, target, beta, unit_seed)
+
+
+# ------------------------------------------------------------------------------ evaluation metrics
+def _acc_ok(acc, least):
+    if acc.dtype != torch.float64 or not acc.is_contiguous() or acc.numel() < least:
+        raise ValueError(f"the accumulator must be a contiguous float64 tensor of at least {least} elements")
+
+
+def error_accum(pred, target, acc):
+    """Add one batch's error statistics to ``acc`` (float64, >= 4 elements, zeroed by the caller):
+    acc[0] += sum |d|, acc[1] += sum d^2, acc[2] = max(acc[2], max |d|), acc[3] += n with d = pred - target
+    formed in fp32 and summed in fp64 (trainer.py:57 without its per-batch ``.item()``).  ``pred`` /
+    ``target``: contiguous fp32 of equal element count, [B] or [B, 1] alike.  One launch (x2g_error_accum),
+    no allocation, nothing read back."""
+    _need_cuda(pred, target, acc)
+    _acc_ok(acc, 4)
+    for t in (pred, target):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("error_accum takes contiguous fp32 predictions and targets")
+    if pred.numel() != target.numel():
+        raise ValueError(f"{pred.numel()} predictions against {target.numel()} targets")
+    call("x2g_error_accum", ptr(pred), ptr(target), pred.numel(), ptr(acc), stream_ptr())
+
+
+def weighted_accum(value, weight, acc):
+    """acc[0] += weight * value, acc[1] += weight (trainer.py:45: ``loss.item() * num_graphs``, kept on the
+    device): ``value`` an fp32 device scalar, ``weight`` a host number, ``acc`` float64 of >= 2 elements.
+    One launch (x2g_weighted_accum), no allocation, nothing read back."""
+    _need_cuda(value, acc)
+    _acc_ok(acc, 2)
+    if value.dtype != torch.float32 or value.numel() != 1:
+        raise ValueError("weighted_accum takes one fp32 value")
+    call("x2g_weighted_accum", ptr(value), float(weight), ptr(acc), stream_ptr())

@@ -8,6 +8,8 @@ update can sit inside a captured HIP graph.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from . import _lib
@@ -89,3 +91,77 @@ class FlatAdam:
 
     def ema_params(self):
         return [self.ema[off:off + p.numel()].view_as(p) for p, off in zip(self.params, self.offsets)]
+
+    def averaged(self, model=None):
+        """Context manager: inside it the optimizer's parameters read the average in place (``ParamSwap``
+        onto ``ema_params()``); on leaving it, after an exception too, they are the training views of ``flat``
+        again, and ``model``'s train / eval mode (when a model is given) is what it was."""
+        return self.average_swap().active(model)
+
+    def average_swap(self):
+        """The ``ParamSwap`` of the parameters onto the average's views, restoring the views of ``flat``
+        this optimizer gave them (kept, so a swap reads no ``.data`` back)."""
+        if self.ema is None:
+            raise ValueError("this optimizer keeps no average (ema_decay=None)")
+        home = [self.flat[off:off + p.numel()].view_as(p) for p, off in zip(self.params, self.offsets)]
+        return ParamSwap(self.params, self.ema_params(), restore=home)
+
+
+class ParamSwap:
+    """Parameters that can read another set of tensors in place: ``enter()`` makes ``values[i]`` the ``.data`` of
+    ``params[i]`` (same shape, dtype and device, checked once here: a pointer rebinding, no bytes are copied),
+    ``leave()`` gives each its former storage back (``restore[i]`` when given, else what ``enter`` found), and
+    ``active(model)`` is the two as a context manager that also restores ``model.training``.
+
+    Every ops call takes its weight pointers at call time and nothing caches them, so a forward between the
+    two reads ``values`` in place — and writes them where a forward writes its weights: the embedding's
+    max_norm renormalisation (ops.embedding_table) then acts on ``values``, as the reference's
+    ``ema_model(data)`` renormalises the averaged table (atom_embedding.py:14).  The Parameter objects stay,
+    so their ``.grad`` views into the GradBucket and the ``_x2g_grad_sink`` marks are untouched, and so are the
+    flat buffers that captured training graphs replay on (those hold addresses, not Parameter objects).
+
+    The cost is host time only: two ``.data`` assignments per parameter and evaluation."""
+
+    def __init__(self, params, values, restore=None):
+        self.params, values = list(params), list(values)
+        for name, ts in (("values", values), ("restore", restore)):
+            if ts is None:
+                continue
+            if len(self.params) != len(ts):
+                raise ValueError(f"{len(ts)} {name} for {len(self.params)} parameters")
+            for p, v in zip(self.params, ts):
+                if p.shape != v.shape or p.dtype != v.dtype or p.device != v.device or not v.is_contiguous():
+                    raise ValueError(f"cannot stand in for a parameter of shape {tuple(p.shape)}: "
+                                     f"{tuple(v.shape)} {v.dtype} on {v.device}")
+        self.values = [v.detach() for v in values]
+        self.restore = None if restore is None else [v.detach() for v in restore]
+        self.held = None
+
+    def enter(self):
+        if self.held is not None:
+            raise RuntimeError("these parameters are swapped already")
+        self.held = self.restore if self.restore is not None else [p.data for p in self.params]
+        for p, v in zip(self.params, self.values):
+            p.data = v
+
+    def leave(self):
+        held, self.held = self.held, None
+        for p, h in zip(self.params, held):
+            p.data = h
+
+    @contextlib.contextmanager
+    def active(self, model=None):
+        was = None if model is None else model.training
+        self.enter()
+        try:
+            yield
+        finally:
+            self.leave()
+            if model is not None:
+                model.train(was)
+
+
+def swap_params(params, values, model=None):
+    """``ParamSwap(params, values).active(model)``: inside the context every parameter has the matching tensor
+    of ``values`` as its ``.data``; on leaving it, after an exception too, its former storage is back."""
+    return ParamSwap(params, values).active(model)
