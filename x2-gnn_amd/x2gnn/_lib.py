@@ -1,4 +1,8 @@
-"""ctypes binding of libx2g.so (the C ABI declared in include/x2g.h).
+"""ctypes binding of libx2g.so, read from the C ABI's one declaration, include/x2g.h.
+
+``parse_header`` turns the header's text into the argument and return types of every function, a
+``ctypes.Structure`` per ``typedef struct`` and the integer ``#define``s; nothing of the ABI is restated in
+Python.  It reads the subset of C the header is written in and raises on anything else.
 
 The library is loaded after ``torch`` so that it binds to the HIP runtime PyTorch already
 loaded (same soname), and every call is enqueued on PyTorch's current stream.  There is no
@@ -7,164 +11,103 @@ fallback: if the library or a GPU is missing, the product path raises.
 from __future__ import annotations
 
 import ctypes
+import keyword
 import os
+import re
 
 import torch  # noqa: F401  (must be imported before the HIP library is loaded)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("X2G_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libx2g.so"))
+HEADER_PATH = os.environ.get("X2G_HEADER",
+                             os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "x2g.h"))
 
-_P = ctypes.c_void_p
-_I64 = ctypes.c_int64
-_I32 = ctypes.c_int32
-_F = ctypes.c_float
-_SZ = ctypes.c_size_t
+_SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int": ctypes.c_int,
+            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 
-# name -> argtypes (restype int unless noted); mirrors include/x2g.h
-SIGNATURES = {
-    "x2g_abi_version": [],
-    "x2g_status_string": [ctypes.c_int],
-    "x2g_csr_rowptr": [_P, _I64, _I64, _P, _P],
-    "x2g_vertex_to_edge_workspace": [_I64, _I64],
-    "x2g_vertex_to_edge": [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P],
-    "x2g_line_graph_transpose": [_P, _P, _I64, _I64, _P, _P, _P, _P, _SZ, _P],
-    "x2g_bessel_env": [_P, _I64, _F, _I32, _I32, _P, _P],
-    "x2g_edge_basis": [_P, _P, _P, _I64, _F, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P],
-    "x2g_edge_basis_freq_grad_workspace": [_I64, _I32],
-    "x2g_edge_basis_freq_grad_splits": [_I64],
-    "x2g_edge_basis_freq_grad": [_P, _P, _P, _P, _I64, _I32, _F, _P, ctypes.c_int, _P, _SZ, _P],
-    "x2g_keyed_row_sum_workspace": [_I64, _I32, _I32],
-    "x2g_residual_fwd": [_P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P],
-    "x2g_dense_fwd_batched": [_P, _I32, _I64, _I32, _I32, ctypes.c_int, _P],
-    "x2g_dense_bwd_batched": [_P, _I32, _I64, _I32, _I32, ctypes.c_int, ctypes.c_int, _P, _SZ, _P],
-    "x2g_readout_head_fwd": [_P, _I32, _I64, _I32, _P, _P],
-    "x2g_readout_head_pool_fwd": [_P, _I32, _I64, _I32, _P, _I64, _P, _P],
-    "x2g_readout_head_pool_bwd": [_P, _P, _I64, _P, _I32, _I64, _I32, ctypes.c_int, _P, _SZ, _P],
-    "x2g_readout_head_bwd_workspace": [_I64, _I32, _I32],
-    "x2g_readout_head_bwd_splits": [_I64],
-    "x2g_readout_head_bwd": [_P, _P, _I32, _I64, _I32, ctypes.c_int, _P, _SZ, _P],
-    "x2g_embedding_table": [_P, _P, _I64, _I32, _I32, _F, _P, _P, _P],
-    "x2g_embedding_table_bwd": [_P, _P, _I32, _I32, _I32, _P, ctypes.c_int, _P],
-    "x2g_keyed_row_sum": [_P, _P, _I64, _I32, _I32, _P, ctypes.c_int, _P, _SZ, _P],
-    "x2g_rbf_gate_fwd": [_P, _P, _P, _P, _I64, _I32, _I32, _P, _P],
-    "x2g_rbf_pool_fwd": [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P],
-    "x2g_rbf_gate_bwd_workspace": [_I64, _I32, _I32],
-    "x2g_batch_meta": [_P, _P, _P, _I64, _I64, _I64] + [_P] * 9 + [_P],
-    "x2g_batch_assemble": [_P, _P, _P, _I64, _P, _I32, _P, _P, _P, _I64, _I64, _I64] + [_P] * 16 + [_P],
-    "x2g_vertex_to_edge_sym": [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P],
-    "x2g_line_graph_transpose_sym": [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _SZ, _P],
-    "x2g_line_graph_sym_build": [_P, _P, _I64, _I64, _I64] + [_P] * 12 + [_P, _SZ, _P],
-    "x2g_vertex_to_edge_sym_mol": [_P, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _I32] + [_P] * 9 + [_P],
-    "x2g_keyed_row_sum_batch_workspace": [_I64, _I32, _I32, _I32],
-    "x2g_keyed_row_sum_batch": [_P, _P, _I32, _P, _I64, _I32, _I32, ctypes.c_int, _P, _SZ, _P],
-    "x2g_clip_adam_ema_ex": [_P, _P, _P, _P, _P, _I64, _P, ctypes.c_int, _P, _SZ, _P],
-    "x2g_rbf_pool_fwd_batch": [_P, _I32, _P, _P, _I64, _I32, _I32, _P],
-    "x2g_rbf_gate_bwd_batch_workspace": [_I64, _I32, _I32, _I32],
-    "x2g_rbf_gate_bwd_batch": [_P, _I32, _P, _P, _I64, _I32, _I32, _P, ctypes.c_int, _P, _P, _SZ, _P],
-    "x2g_rbf_gate_bwd_splits": [_I64],
-    "x2g_rbf_gate_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, ctypes.c_int, _P, _SZ, _P],
-    "x2g_spherical_basis": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P],
-    "x2g_sbf_attention_bwd_dst_g": [_P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32,
-                                    _I32, _P, _P, _P, _P, _P, _P],
-    "x2g_sbf_attention_bwd_src_fold": [_P, _P, _P, _P, _P, _I32, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                       _P, _I64, _I64, _I32, _I32, _P, _P, _P, _P],
-    "x2g_sbf_radial_wgrad_splits": [_I64],
-    "x2g_sbf_radial_wgrad_workspace": [_I64, _I32],
-    "x2g_sbf_radial_wgrad": [_P, _P, _I64, _I32, _P, _P, ctypes.c_int, _P, _SZ, _P],
-    "x2g_sbf_attention_fwd": [_P, _P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32,
-                              _I32, _P, _P, _P, _P, _P],
-    "x2g_sbf_attention_fwd_stats": [_P, _P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _I64, _I64, _I32,
-                                    _I32, _I32, _P, _P, _P, _P, _P, _P],
-    "x2g_sbf_attention_fwd_center": [_P, _P, _P, _P, _P, _P, ctypes.c_int, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I32,
-                                     _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P],
-    "x2g_sbf_attention_fwd_center_sf": [_P] * 6 + [ctypes.c_int] + [_P] * 10 + [_I64, _I64, _I32, _I64, _I64, _I32,
-                                                                                _I32] + [_P] * 8,
-    "x2g_sbf_attention_fwd_center_sf_tiled": [_P] * 6 + [ctypes.c_int] + [_P] * 10 + [_I64, _I64, _I32, _I32, _I64,
-                                                                                      _I64, _I32, _I32] + [_P] * 8,
-    "x2g_sbf_attention_fwd_center_sf_tiled_lds": [],
-    "x2g_center_schedule_workspace": [_I64],
-    "x2g_center_packs_host": [_P, _I64, _I32, _I32, _P, _P, _P, _P],
-    "x2g_center_schedule": [_P, _P, _I64, _P, _P, _P, _P, _P, _SZ, _P],
-    "x2g_sbf_attention_bwd_center_lds": [_I32, _I32],
-    "x2g_sbf_attention_bwd_center": [_P] * 5 + [ctypes.c_int] + [_P] * 12 + [_I64, _I32, _I64, _I64, _I32, _I32] +
-                                    [_P] * 7,
-    "x2g_sbf_attention_bwd_dst": [_P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64,
-                                  _I32, _I32, _I32, _P, _P, _P, _P, _P],
-    "x2g_sbf_attention_bwd_src": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _P,
-                                  _P, _P],
-    "x2g_segment_sum": [_P, _P, _P, _I64, _I64, _P, _P],
-    "x2g_segment_broadcast": [_P, _P, _P, _I64, _I64, _P, _P],
-    "x2g_segment_softmax_fwd": [_P, _P, _I64, _I64, _P, _P],
-    "x2g_segment_softmax_bwd": [_P, _P, _P, _I64, _I64, _P, _P],
-    "x2g_csr_rowptr_checked": [_P, _I64, _I64, _P, _P, _P],
-    "x2g_segment_reduce_perm": [_P, _P, _P, _I64, _I64, ctypes.c_int, _P, _P],
-    "x2g_segment_reduce_perm_bwd": [_P, _P, _P, _I64, _I64, ctypes.c_int, _P, _P],
-    "x2g_segment_softmax_perm_fwd": [_P, _P, _P, _I64, _I64, _P, _P],
-    "x2g_segment_softmax_perm_bwd": [_P, _P, _P, _P, _I64, _I64, _P, _P],
-    "x2g_graph_layernorm_fwd": [_P, _P, _I64, _I64, _F, _P, _P, _P, _P],
-    "x2g_graph_layernorm_bwd": [_P, _P, _P, _P, _I64, _I64, _P, _P],
-    "x2g_graph_layernorm_bwd_workspace": [_I64],
-    "x2g_chain_fwd_batch": [_P, _I32, _I32, _I64, _I32, _P],
-    "x2g_smooth_l1_mean_fwd": [_P, _P, _I64, _F, _P, _P],
-    "x2g_smooth_l1_mean_fwd_grad": [_P, _P, _I64, _F, _P, _P, _P],
-    "x2g_smooth_l1_mean_bwd": [_P, _P, _I64, _F, _P, _P, _P],
-    "x2g_error_accum": [_P, _P, _I64, _P, _P],
-    "x2g_weighted_accum": [_P, ctypes.c_double, _P, _P],
-    "x2g_chain_bwd_batch": [_P, _I32, _I32, _I64, _I32, _P],
-    "x2g_graph_layernorm_bwd_ex": [_P, _P, _P, _P, _I64, _I64, _P, _P, _SZ, _P],
-    "x2g_graph_layernorm_bwd_rows": [_P, _P, _P, _P, _I64, _I64, _P, _P, _P],
-    "x2g_linear_wgrad_workspace": [_I64, _I32, _I32],
-    "x2g_dense_fwd": [_P, _P, _P, _I64, _I32, _I32, ctypes.c_int, _P, _P, _P, _P],
-    "x2g_dense_bwd_workspace": [_I64, _I32, _I32],
-    "x2g_dense_bwd": [_P, _P, ctypes.c_int, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _SZ, _P],
-    "x2g_linear_wgrad_ex": [_P, _P, _I64, _I32, _I32, _P, _P, ctypes.c_int, _P, _SZ, _P],
-    "x2g_optimizer_workspace": [_I64],
-    "x2g_slab_sum_batch": [_P, _I32, _I32, _P],
-    "x2g_linear_wgrad_splits": [_I64, _I32, _I32],
-    "x2g_dense_bwd_splits": [_I64, _I32, _I32],
-    "x2g_dense_bwd_slab_offset": [_I64, _I32, _I32],
-    "x2g_sbf_project": [_P, _I64, _I32, _P, _P, _I32, _P, _P],
-    "x2g_sbf_project_batch": [_P, _I64, _I32, _P, _P, _I32, _I32, _P, _P],
-    "x2g_clip_adam_ema": [_P, _P, _P, _P, _P, _I64, _P, _P, _SZ, _P],
-    "x2g_dense_bwd_ex": [_P, _P, ctypes.c_int, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, ctypes.c_int, _P, _SZ,
-                         _P],
-    "x2g_chain_fwd": [_P, _P, _P, _I32, _I64, _I32, _P, _P],
-    "x2g_chain_fwd_ln": [_P, _P, _P, _I64, ctypes.c_float, _P, _P, _P, _P, _P, _I32, _I64, _I32, _P, _P],
-    "x2g_chain_bwd": [_P, _P, _P, _I32, _I64, _I32, _P, _P, _P, _P],
-    "x2g_chain_bwd_ln": [_P, _P, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P],
-    "x2g_chain_t_floats": [_I64, _I32],
-    "x2g_chain_wgrad_workspace": [_I64, _I32, _I32],
-    "x2g_chain_wgrad": [_P, _P, _I32, _I64, _I32, _P, _P, ctypes.c_int, _P, _SZ, _P],
-    "x2g_conv_proj_fwd": [_P, _P, _I32, _P, _P, _I64, _I32, _P, _P, _P],
-    "x2g_conv_proj_bwd_gate_splits": [_I64],
-    "x2g_conv_proj_bwd_gate_workspace": [_I64, _I32],
-    "x2g_conv_proj_bwd_gate": [_P, _I64, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, ctypes.c_int, _P, _SZ, _P],
-    "x2g_table_chain_fwd": [_P, _I64, _I32, _P, _I32, _P],
-    "x2g_table_chain_bwd_workspace": [_I32],
-    "x2g_table_chain_bwd_ex": [_P, _I32, _I64, _I32, _P, _P, _SZ, _P],
-    "x2g_tiled_wgrad_flat_workspace": [_I64, _I32, _I32],
-    "x2g_tiled_wgrad_flat_rows_workspace": [_P, _I32, _I32],
-    "x2g_tiled_wgrad_flat": [_P, _I32, _I64, _I32, ctypes.c_int, _P, _P, _SZ, _P],
-    "x2g_tiled_wgrad_flat_rows": [_P, _P, _I32, _I32, ctypes.c_int, _P, _P, _SZ, _P],
-    "x2g_feat_fwd": [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "x2g_feat_bwd": [_P, _P, _P, _P, _I64, _P, _P, _P],
-}
-RESTYPES = {"x2g_status_string": ctypes.c_char_p, "x2g_vertex_to_edge_workspace": _SZ,
-            "x2g_table_chain_bwd_workspace": _SZ,
-            "x2g_linear_wgrad_workspace": _SZ, "x2g_dense_bwd_workspace": _SZ, "x2g_optimizer_workspace": _SZ,
-            "x2g_linear_wgrad_splits": ctypes.c_int32, "x2g_dense_bwd_splits": ctypes.c_int32,
-            "x2g_dense_bwd_slab_offset": ctypes.c_int64, "x2g_edge_basis_freq_grad_workspace": _SZ,
-            "x2g_edge_basis_freq_grad_splits": ctypes.c_int32, "x2g_rbf_gate_bwd_workspace": _SZ, "x2g_rbf_gate_bwd_batch_workspace": _SZ, "x2g_keyed_row_sum_batch_workspace": _SZ,
-            "x2g_rbf_gate_bwd_splits": ctypes.c_int32, "x2g_keyed_row_sum_workspace": _SZ,
-            "x2g_readout_head_bwd_workspace": _SZ, "x2g_readout_head_bwd_splits": ctypes.c_int32,
-            "x2g_sbf_radial_wgrad_splits": ctypes.c_int32, "x2g_sbf_radial_wgrad_workspace": _SZ,
-            "x2g_chain_t_floats": ctypes.c_int64, "x2g_chain_wgrad_workspace": _SZ,
-            "x2g_tiled_wgrad_flat_workspace": _SZ,
-            "x2g_tiled_wgrad_flat_rows_workspace": _SZ,
-            "x2g_conv_proj_bwd_gate_splits": ctypes.c_int32,
-            "x2g_conv_proj_bwd_gate_workspace": _SZ, "x2g_graph_layernorm_bwd_workspace": _SZ,
-            "x2g_sbf_attention_bwd_center_lds": _SZ, "x2g_sbf_attention_fwd_center_sf_tiled_lds": _SZ,
-            "x2g_center_schedule_workspace": _SZ}
+
+class _Consts(dict):
+    """``#define`` name (without ``X2G_``) -> int.  A macro whose value is no integer literal is kept aside
+    and raises when it is asked for."""
+
+    def __init__(self):
+        super().__init__()
+        self.other = {}
+
+    def __missing__(self, name):
+        if name in self.other:
+            raise ValueError(f"#define {name} is not an integer literal: {self.other[name]!r}")
+        raise KeyError(name)
+
+
+def _ctype(spec, decl, known, ret=False):
+    """The ctypes type of the C type ``spec`` (``decl``: the declaration it stands in, for the message)."""
+    words = [w for w in re.findall(r"\w+|\*", spec) if w != "const"]
+    base, stars = words[:1], words[1:]
+    if len(base) == 1 and all(s == "*" for s in stars):
+        if not stars and base[0] in _SCALARS:
+            return _SCALARS[base[0]]
+        if stars and (base[0] in _SCALARS or base[0] in known or base[0] in ("void", "char")):
+            return ctypes.c_char_p if ret and base[0] == "char" and len(stars) == 1 else ctypes.c_void_p
+    raise ValueError(f"x2g.h: unknown type {spec.strip()!r} in: {decl}")
+
+
+def _split(item, decl):
+    """(type, name) of a parameter or field ``item``; arrays, bit-fields and function pointers do not match."""
+    m = re.fullmatch(r"([\w\s*]+?)\s*\b(\w+)", item.strip())
+    if not m:
+        raise ValueError(f"x2g.h: cannot read {item.strip()!r} in: {decl}")
+    return m[1], m[2]
+
+
+def parse_header(text):
+    """(SIGNATURES, RESTYPES, STRUCTS, CONSTS) of a header written like include/x2g.h: comments, integer
+    ``#define``s, ``typedef struct { scalar or pointer fields } name;`` and function declarations.  Anything
+    else raises ValueError quoting the declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b[^\n]*", "", text, flags=re.S | re.M)
+    consts = _Consts()
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)(.*)$", text, flags=re.M):
+        name = name[4:] if name.startswith("X2G_") else name
+        try:
+            consts[name] = int(value.strip(), 0)
+        except ValueError:
+            consts.other[name] = value.strip()
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+
+    structs = {}
+
+    def struct(m):
+        decl = " ".join(m[0].split())
+        fields = []
+        for item in filter(str.strip, m[1].split(";")):
+            spec, name = _split(item, decl)
+            fields.append((name + "_" if keyword.iskeyword(name) else name, _ctype(spec, decl, structs)))
+        structs[m[2]] = type(m[2], (ctypes.Structure,), {"_fields_": fields, "__doc__": f"{m[2]} (include/x2g.h)."})
+        return ""
+
+    text = re.sub(r"\btypedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+
+    signatures, restypes = {}, {}
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        m = re.fullmatch(r"([\w\s*]+?)\s*\b(\w+)\s*\(([^()]*)\)", decl)
+        if not m:
+            raise ValueError(f"x2g.h: cannot read the declaration: {decl}")
+        args = [] if m[3].strip() == "void" else m[3].split(",")
+        signatures[m[2]] = [_ctype(_split(a, decl)[0], decl, structs) for a in args]
+        restypes[m[2]] = _ctype(m[1], decl, structs, ret=True)
+    return signatures, restypes, structs, consts
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"x2g.h not found at {HEADER_PATH}: set X2G_HEADER to the header libx2g.so was built from")
+    with open(HEADER_PATH) as f:
+        return f.read()
+
+
+# name -> argtypes / restype of every function, name -> Structure of every typedef struct, and the #defines
+SIGNATURES, RESTYPES, STRUCTS, CONSTS = parse_header(_read_header())
 
 _lib = None
 
@@ -179,7 +122,7 @@ def load():
         for name, args in SIGNATURES.items():
             fn = getattr(lib, name)
             fn.argtypes = args
-            fn.restype = RESTYPES.get(name, ctypes.c_int)
+            fn.restype = RESTYPES[name]
         _lib = lib
     return _lib
 

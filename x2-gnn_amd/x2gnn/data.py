@@ -280,7 +280,10 @@ def center_packs(deg, cap=CENTER_PACK_ROWS, max_members=CENTER_PACK_MEMBERS):
     return order, packs[:units.value + 1].copy(), int(rows.value)
 
 
-CENTER_SF_MAX_ROWS = 17  # ops.CENTER_SF_MAX_ROWS
+# Units of more rows than this go to the source-tiled fused forward (x2g_sbf_attention_fwd_center_sf_tiled):
+# the fused forward's LDS image of 17 rows (81.7 KB) is the largest that keeps two workgroups per CU
+# (config 2's largest degree is 17, config 5's AID atoms reach 61).  ops.py imports it.
+CENTER_SF_MAX_ROWS = 17
 
 
 def center_hubs(deg, order, packs, max_rows=CENTER_SF_MAX_ROWS):

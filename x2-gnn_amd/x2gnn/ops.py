@@ -25,8 +25,10 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr, stream_ptr
+from .data import CENTER_SF_MAX_ROWS
 
-EDGE_NONE, EDGE_PER_TRIPLET, EDGE_PER_DST = 0, 1, 2
+_C = _lib.CONSTS  # the #defines of include/x2g.h, by name without the X2G_ prefix
+EDGE_NONE, EDGE_PER_TRIPLET, EDGE_PER_DST = _C["EDGE_NONE"], _C["EDGE_PER_TRIPLET"], _C["EDGE_PER_DST"]
 
 
 def rows_fit(rows, width):
@@ -372,7 +374,7 @@ def _sbf_factors(lg, sbf, edge_mode, D, edge, edge_row):
     return fac[1], fac[2]
 
 
-CENTER_MAX_DEGREE = 128  # X2G_CENTER_MAX_DEGREE
+CENTER_MAX_DEGREE = _C["CENTER_MAX_DEGREE"]
 # Center-atom attention kernels (csrc/attention_center.hip) for symmetric line graphs: False = the
 # destination-major kernels everywhere; _CENTER_BWD False = the center forward with the destination-major
 # backward passes (parity tests flip them).
@@ -393,12 +395,6 @@ def _center_units(lg, packed):
         return lg.pack_order, packs, int(packs.shape[0]) - 1, max(int(lg.center_rows), 1), \
             getattr(lg, "pack_info", None)
     return lg.center_order, None, lg.N, max(int(lg.max_degree), 1), None
-
-
-# Units of more rows than this go to the source-tiled fused forward (x2g_sbf_attention_fwd_center_sf_tiled):
-# the fused forward's LDS image of 17 rows (81.7 KB) is the largest that keeps two workgroups per CU
-# (data.CENTER_SF_MAX_ROWS; config 2's largest degree is 17, config 5's AID atoms reach 61).
-CENTER_SF_MAX_ROWS = 17
 
 
 def _center_split(lg):
@@ -720,20 +716,9 @@ def embedding_table(weight, z, max_norm, padding_idx, scale_grad_by_freq):
     return _EmbeddingTable.apply(weight, z, max_norm, padding_idx, scale_grad_by_freq)
 
 
-class DenseFwdGroup(ctypes.Structure):
-    _fields_ = [("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("b", ctypes.c_void_p), ("res", ctypes.c_void_p),
-                ("y", ctypes.c_void_p), ("z", ctypes.c_void_p)]
-
-
-class DenseBwdGroup(ctypes.Structure):
-    _fields_ = [("dy", ctypes.c_void_p), ("z", ctypes.c_void_p), ("x", ctypes.c_void_p), ("w", ctypes.c_void_p),
-                ("dx", ctypes.c_void_p), ("dx_add", ctypes.c_void_p), ("dw", ctypes.c_void_p),
-                ("db", ctypes.c_void_p)]
-
-
-class HeadGroup(ctypes.Structure):
-    _fields_ = [("h", ctypes.c_void_p), ("w", ctypes.c_void_p), ("b", ctypes.c_void_p), ("dh", ctypes.c_void_p),
-                ("dw", ctypes.c_void_p), ("db", ctypes.c_void_p)]
+DenseFwdGroup = _lib.STRUCTS["x2g_dense_fwd_group"]
+DenseBwdGroup = _lib.STRUCTS["x2g_dense_bwd_group"]
+HeadGroup = _lib.STRUCTS["x2g_head_group"]
 
 
 def _dp(t):
@@ -884,19 +869,9 @@ def _head_fwd(heads, G, R, D, pool, f32, st):
 
 # the readouts' two hidden layers as one batched row-chain launch each way (x2g_chain_*_batch) where
 # compiled; two batched dense launches each way otherwise
-CHAIN_MAX_JOBS = 8  # X2G_CHAIN_MAX_JOBS
-
-
-class ChainFwdJob(ctypes.Structure):
-    """x2g_chain_fwd_job."""
-    _fields_ = [("x", ctypes.c_void_p), ("res_ext", ctypes.c_void_p), ("stages", ctypes.c_void_p),
-                ("in_t", ctypes.c_void_p)]
-
-
-class ChainBwdJob(ctypes.Structure):
-    """x2g_chain_bwd_job."""
-    _fields_ = [("dy", ctypes.c_void_p), ("dy_add", ctypes.c_void_p), ("stages", ctypes.c_void_p),
-                ("dx", ctypes.c_void_p), ("d_res_ext", ctypes.c_void_p), ("dz_t", ctypes.c_void_p)]
+CHAIN_MAX_JOBS = _C["CHAIN_MAX_JOBS"]
+ChainFwdJob = _lib.STRUCTS["x2g_chain_fwd_job"]
+ChainBwdJob = _lib.STRUCTS["x2g_chain_bwd_job"]
 
 
 def _readout_chain_ok(R, D, G, *weights):
@@ -969,7 +944,7 @@ def keyed_row_sum(src, key, num_keys: int):
 # ``table_chain``), not to the module: two models, threads or streams never share it.  False sums
 # each immediately.
 _DEFER_KEYED = True
-KEYED_MAX_JOBS = 8  # X2G_KEYED_MAX_JOBS
+KEYED_MAX_JOBS = _C["KEYED_MAX_JOBS"]
 
 
 def keyed_row_sum_deferred(src, key, num_keys: int, pending: list):
@@ -1128,16 +1103,8 @@ def sbf_attention(q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg: LineGraph, heads: 
 
 
 # ---------------------------------------------------------------------------------- dense layers
-ACCUM_WGRAD = 1  # X2G_ACCUM_WGRAD
-DEFER_SLAB_SUM = 2  # X2G_DEFER_SLAB_SUM
-GATE_DRBF_ACCUM = 4  # X2G_GATE_DRBF_ACCUM
-
-
-class SlabJob(ctypes.Structure):
-    """x2g_slab_job (include/x2g.h)."""
-    _fields_ = [("part_w", ctypes.c_void_p), ("part_b", ctypes.c_void_p), ("dw", ctypes.c_void_p),
-                ("db", ctypes.c_void_p), ("n_w", ctypes.c_int64), ("n_b", ctypes.c_int32), ("splits", ctypes.c_int32),
-                ("ld", ctypes.c_int32), ("cols", ctypes.c_int32)]
+ACCUM_WGRAD, DEFER_SLAB_SUM, GATE_DRBF_ACCUM = _C["ACCUM_WGRAD"], _C["DEFER_SLAB_SUM"], _C["GATE_DRBF_ACCUM"]
+SlabJob = _lib.STRUCTS["x2g_slab_job"]
 
 
 class _SlabDeferral:
@@ -1166,7 +1133,7 @@ def _defer():
     return _DEFERRALS.get(torch.cuda.current_stream().cuda_stream)
 
 
-TILED_MAX_JOBS = 64  # X2G_TILED_MAX_JOBS
+TILED_MAX_JOBS = _C["TILED_MAX_JOBS"]
 
 # In-step kernel timing for bench.py's roofline line: while a name is a key here, an EAGER (not captured)
 # pass appends (start, end) HIP events recorded around that kernel's launch on its stream.  A sleep kernel
@@ -1399,7 +1366,7 @@ def linear_wgrad(dy, x, bias=True, w_param=None, b_param=None):
     return dest.grads()
 
 
-ACT_NONE, ACT_SILU = 0, 1
+ACT_NONE, ACT_SILU = _C["ACT_NONE"], _C["ACT_SILU"]
 
 
 def _dense_fwd_raw(x2, w, b, act, r2=None, want_z=True):
@@ -1508,22 +1475,14 @@ def residual_layer(x, w0, b0, w1, b1):
     return _ResidualFn.apply(x, w0, b0, w1, b1)
 
 
-CHAIN_SILU, CHAIN_HOLD, CHAIN_RES_HELD, CHAIN_RES_EXT = 1, 2, 4, 8  # X2G_CHAIN_* (include/x2g.h)
-CHAIN_RES_ACCUM = 16  # backward only
-CHAIN_IN0_ROWMAJOR = 32  # forward only, stage 0: no T plane 0 (the weight gradient reads the input row-major)
-CHAIN_MAX_STAGES = 8
+# stage flags; RES_ACCUM: backward only; IN0_ROWMAJOR: forward only, stage 0: no T plane 0 (the weight gradient
+# reads the input row-major)
+CHAIN_SILU, CHAIN_HOLD, CHAIN_RES_HELD, CHAIN_RES_EXT, CHAIN_RES_ACCUM, CHAIN_IN0_ROWMAJOR, CHAIN_MAX_STAGES = (
+    _C["CHAIN_" + n] for n in ("SILU", "HOLD", "RES_HELD", "RES_EXT", "RES_ACCUM", "IN0_ROWMAJOR", "MAX_STAGES"))
 
 
-class ChainStage(ctypes.Structure):
-    """x2g_chain_stage."""
-    _fields_ = [("w", ctypes.c_void_p), ("b", ctypes.c_void_p), ("z", ctypes.c_void_p), ("y", ctypes.c_void_p),
-                ("wt", ctypes.c_void_p), ("flags", ctypes.c_int32)]
-
-
-class ChainBwdStage(ctypes.Structure):
-    """x2g_chain_bwd_stage."""
-    _fields_ = [("w", ctypes.c_void_p), ("wt", ctypes.c_void_p), ("z", ctypes.c_void_p), ("dz", ctypes.c_void_p),
-                ("flags", ctypes.c_int32)]
+ChainStage = _lib.STRUCTS["x2g_chain_stage"]
+ChainBwdStage = _lib.STRUCTS["x2g_chain_bwd_stage"]
 
 
 def chain_wgrad(in_t, dz_t, R, weights, biases, x0=None):
@@ -1680,21 +1639,12 @@ def row_chain(x, res, linears, flags, ln=None):
 
 
 # ------------------------------------------------------------------------------ small-table chains
-TABLE_MAX_STAGES = 8  # X2G_TABLE_MAX_STAGES
+TABLE_MAX_STAGES = _C["TABLE_MAX_STAGES"]
 _FAN_IN = True  # False: autograd's own fan-in adds (test_fan_in_gradients_match_autograd_adds)
 
 
-class TableStage(ctypes.Structure):
-    """x2g_table_stage."""
-    _fields_ = [("w", ctypes.c_void_p), ("b", ctypes.c_void_p), ("parent", ctypes.c_int32), ("act", ctypes.c_int32),
-                ("z", ctypes.c_void_p), ("y", ctypes.c_void_p)]
-
-
-class TableBwdStage(ctypes.Structure):
-    """x2g_table_bwd_stage."""
-    _fields_ = [("w", ctypes.c_void_p), ("in_", ctypes.c_void_p), ("z", ctypes.c_void_p), ("dy", ctypes.c_void_p),
-                ("dw", ctypes.c_void_p), ("db", ctypes.c_void_p), ("parent", ctypes.c_int32), ("act", ctypes.c_int32),
-                ("accum", ctypes.c_int32)]
+TableStage = _lib.STRUCTS["x2g_table_stage"]
+TableBwdStage = _lib.STRUCTS["x2g_table_bwd_stage"]
 
 
 def table_chain_supported(x, linears):
@@ -1850,13 +1800,8 @@ def featurize(x, env, lin1, lin2):
     return _apply(_FeaturizeFn, x, env, lin1.weight, lin1.bias, lin2.weight, lin2.bias)
 
 
-class TiledJob(ctypes.Structure):
-    """x2g_tiled_job.  ``layout``: TILED_DY_ROWMAJOR | TILED_X_ROWMAJOR (0: both operands in the T layout)."""
-    _fields_ = [("dy_t", ctypes.c_void_p), ("x_t", ctypes.c_void_p), ("dw", ctypes.c_void_p), ("db", ctypes.c_void_p),
-                ("ld", ctypes.c_int32), ("cols", ctypes.c_int32), ("layout", ctypes.c_int32), ("pad_", ctypes.c_int32)]
-
-
-TILED_DY_ROWMAJOR, TILED_X_ROWMAJOR = 1, 2  # X2G_TILED_*_ROWMAJOR
+TiledJob = _lib.STRUCTS["x2g_tiled_job"]  # layout: TILED_DY_ROWMAJOR | TILED_X_ROWMAJOR (0: both in the T layout)
+TILED_DY_ROWMAJOR, TILED_X_ROWMAJOR = _C["TILED_DY_ROWMAJOR"], _C["TILED_X_ROWMAJOR"]
 
 # The weight gradients' x operands that exist row-major anyway (the projections' x, the chains' input) are
 # read there, and no T-layout copy of them is written.  False: the forwards write those copies (x_t, T
@@ -1885,14 +1830,8 @@ def _run_tiled(R, jobs, keep, acc):
         _tiled_now(R, jobs, acc, keep[0].device)
 
 
-class Proj(ctypes.Structure):
-    """x2g_proj."""
-    _fields_ = [("w", ctypes.c_void_p), ("b", ctypes.c_void_p), ("out", ctypes.c_void_p), ("wt", ctypes.c_void_p)]
-
-
-class ProjGrad(ctypes.Structure):
-    """x2g_proj_grad."""
-    _fields_ = [("g", ctypes.c_void_p), ("w", ctypes.c_void_p), ("wt", ctypes.c_void_p), ("g_t", ctypes.c_void_p)]
+Proj = _lib.STRUCTS["x2g_proj"]
+ProjGrad = _lib.STRUCTS["x2g_proj_grad"]
 
 
 def tiled_wgrad(dy_ts, x_ts, R, weights, biases, layouts=None):
@@ -2139,14 +2078,8 @@ def _addr(t):
     return None if t is None else t.data_ptr()
 
 
-class GateJob(ctypes.Structure):
-    """x2g_gate_job."""
-    _fields_ = [("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("b", ctypes.c_void_p), ("out", ctypes.c_void_p),
-                ("g", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("dx_add", ctypes.c_void_p), ("dw", ctypes.c_void_p),
-                ("db", ctypes.c_void_p)]
-
-
-GATE_MAX_JOBS = 8  # X2G_GATE_MAX_JOBS
+GateJob = _lib.STRUCTS["x2g_gate_job"]
+GATE_MAX_JOBS = _C["GATE_MAX_JOBS"]
 # the readouts' edge -> atom pools as one launch each way (x2g_rbf_pool_fwd_batch / _gate_bwd_batch)
 _POOL_BATCH = True
 
@@ -2315,7 +2248,7 @@ class IndexPlan:
         self.rowptr, _ = csr_rowptr_checked(keys, self.dim_size)
 
 
-REDUCE_SUM, REDUCE_MEAN = 0, 1  # X2G_REDUCE_*
+REDUCE_SUM, REDUCE_MEAN = _C["REDUCE_SUM"], _C["REDUCE_MEAN"]
 
 
 class _ScatterReduce(torch.autograd.Function):

@@ -16,8 +16,10 @@ from . import _lib
 from ._lib import call, ptr, stream_ptr
 from .dist import GradBucket, flat_layout
 
-_LR, _B1, _B2, _EPS, _MAXN, _EMAD, _STEP, _NORM, _CLIP = range(9)
-_WARMUP, _DECAY_STEPS, _DECAY_RATE, _BASE_LR, _STAIRCASE = range(11, 16)
+# slots of the float[16] device scalar block (X2G_OPT_* of include/x2g.h)
+_LR, _B1, _B2, _EPS, _MAXN, _EMAD, _STEP, _NORM, _CLIP, _WARMUP, _DECAY_STEPS, _DECAY_RATE, _BASE_LR, _STAIRCASE = (
+    _lib.CONSTS["OPT_" + n] for n in ("LR", "BETA1", "BETA2", "EPS", "MAX_NORM", "EMA_DECAY", "STEP", "NORM", "CLIP",
+                                      "WARMUP", "DECAY_STEPS", "DECAY_RATE", "BASE_LR", "STAIRCASE"))
 
 
 class FlatAdam:
@@ -54,8 +56,8 @@ class FlatAdam:
         """One update; ``zero_grads``: also zero the gradient bucket as it is read (zero_grad()
         folded into the step's last kernel, so the next backward needs no fill)."""
         call("x2g_clip_adam_ema_ex", ptr(self.flat), ptr(self.bucket.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-             ptr(self.ema), self.flat.numel(), ptr(self.scalars), 1 if zero_grads else 0, ptr(self.ws),
-             self.ws_bytes, stream_ptr())
+             ptr(self.ema), self.flat.numel(), ptr(self.scalars),
+             _lib.CONSTS["OPT_ZERO_GRADS"] if zero_grads else 0, ptr(self.ws), self.ws_bytes, stream_ptr())
 
     def set_lr(self, lr):
         """A fixed learning rate from the next step on (clears a schedule; e.g. for a host-side
