@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "../../include/x2g_staged.h"
 
 namespace x2g {
 namespace {
@@ -317,10 +318,17 @@ struct FwdSfArgs {
   float *out, *alpha, *smax, *sden, *sp;  // sp: S [T, 128] out (NULL: not stored)
   float* pp;  // P [E, 7, 128] out (NULL: not stored): the backward's S_t = b + sum_l Y_l(t) P_s[l]
   float2* row_stats;
+  // the DROP instances' (attention dropout: common.hpp drop_key, include/x2g_staged.h)
+  const int64_t* drop_key;
+  uint32_t drop_salt, drop_thr;
+  float drop_scale;
 };
 
 // (4 waves per SIMD, two 8-wave workgroups per CU: at most 128 VGPRs)
-template <int LPH, int WAVES, int B, bool EDGE>
+// DROP: attention dropout, out = sum_t a_t r_t u_t S_t + skip with r_t the triplet's keep scale per head (0 or
+// 1 / (1 - p), regenerated from the key in the value loop, nothing held for it across the batch); the batches
+// and their order are the plain instance's, so max, denominator, logits and S rows keep its bits.
+template <int LPH, int WAVES, int B, bool EDGE, bool DROP>
 __global__ void __launch_bounds__(64 * WAVES, 4) attn_fwd_center_sf_kernel(const FwdSfArgs a) {
   // [tables] then [rows][32] (k + e), [rows][32] (v + e), [rows][7][32] P, [rows][42] R
   extern __shared__ cf4 lds[];
@@ -342,6 +350,8 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_fwd_center_sf_kernel(const
   const int head = l32 / LPH;
   const bool leader = (l32 % LPH) == 0;
   const int c0 = 4 * l32;
+  DropKey dkey{};
+  if constexpr (DROP) dkey = drop_key(a.drop_key, a.drop_salt, a.drop_thr, a.drop_scale);
   // this owner's first destination row: its id and triplet block (in flight under the staging)
   int g = owner;
   int d = 0, tb = 0;
@@ -448,6 +458,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_fwd_center_sf_kernel(const
         yl[5] = dpp_mov<0x155>(yv[uu]);
         yl[6] = dpp_mov<0x156>(yv[uu]);
         cf4 s4 = bias4;
+        if constexpr (DROP && LPH == 1) s4 = ld4(a.bias + c0);  // (32 heads: re-read, four registers fewer held)
 #pragma unroll
         for (int l = 0; l < kSfL; ++l) s4 += yl[l] * P[(jr * kSfL + l) * 32 + l32];
         sv[uu] = s4;
@@ -468,7 +479,14 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_fwd_center_sf_kernel(const
         const float p = lg[uu] == -INFINITY ? 0.f : expf(lg[uu] - m_new);
         const cf4 vr = VE[(base + (j < n ? j : n - 1)) * 32 + l32];
         den += p;
-        acc += p * (vr * sv[uu]);
+        if constexpr (DROP) {
+          // (the triplet's row formed again from j: nothing of the logit loop is held across for it)
+          int jj = j - (j > i ? 1 : 0);
+          jj = jj < nt ? jj : nt - 1;
+          acc += (p * (drop_keep(dkey, tb + jj, head, a.H) ? dkey.scale : 0.f)) * (vr * sv[uu]);
+        } else {
+          acc += p * (vr * sv[uu]);
+        }
       }
       m = m_new;
     };
@@ -478,6 +496,9 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_fwd_center_sf_kernel(const
       if (j0 < n) batch(j0, std::integral_constant<int, B / 2>{});
     }
     const float inv = 1.0f / (den + kCEps);
+    // (DROP: the skip row is loaded here instead of being held through the batches — the mask's arithmetic
+    // takes its four registers)
+    if constexpr (DROP) sk = ld4(a.skip + drow);
     const cf4 o = acc * inv + sk;
     st4(a.out + drow, o);
     if (a.row_stats) {
@@ -506,7 +527,7 @@ constexpr size_t fwd_sf_lds(int rows) {
   return unit_rows_lds(rows) + static_cast<size_t>(rows) * ((2 + kSfL) * kCD + kSfK) * 4;
 }
 
-template <int LPH>
+template <int LPH, bool DROP>
 int fwd_sf_launch(const FwdSfArgs& a, bool edge, hipStream_t st) {
   constexpr int W = 8, B = 8;
   const size_t lds = fwd_sf_lds(a.max_rows);
@@ -520,7 +541,8 @@ int fwd_sf_launch(const FwdSfArgs& a, bool edge, hipStream_t st) {
     kern<<<grid, 64 * W, lds, st>>>(a);
     return last_launch_status();
   };
-  return edge ? go(attn_fwd_center_sf_kernel<LPH, W, B, true>) : go(attn_fwd_center_sf_kernel<LPH, W, B, false>);
+  return edge ? go(attn_fwd_center_sf_kernel<LPH, W, B, true, DROP>)
+              : go(attn_fwd_center_sf_kernel<LPH, W, B, false, DROP>);
 }
 
 // ------------------------------------------------------------------------------ forward, fused, source tiles
@@ -535,9 +557,11 @@ int fwd_sf_launch(const FwdSfArgs& a, bool edge, hipStream_t st) {
 // at other points: equal to fp32 rounding.
 constexpr int kTileRows = 16;
 
-template <int LPH, int WAVES, int B, bool EDGE, int RMAX, bool STORE>
+// DROP: as in the untiled kernel (instances only with STORE)
+template <int LPH, int WAVES, int B, bool EDGE, int RMAX, bool STORE, bool DROP>
 __global__ void __launch_bounds__(64 * WAVES, 4) attn_fwd_center_sf_tiled_kernel(const FwdSfArgs a) {
   static_assert(kTileRows % B == 0, "batches never cross a tile");
+  static_assert(STORE || !DROP, "the dropout instances are the storing ones");
   // [TS][32] (k + e), [TS][32] (v + e), [TS][7][32] P, [TS][42] R, then per destination row its id and
   // triplet block [X2G_CENTER_MAX_DEGREE] x 2
   extern __shared__ cf4 lds[];
@@ -577,6 +601,8 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_fwd_center_sf_tiled_kernel
   const bool leader = (l32 % LPH) == 0;
   const int c0 = 4 * l32;
   const int nt = n - 1;
+  DropKey dkey{};
+  if constexpr (DROP) dkey = drop_key(a.drop_key, a.drop_salt, a.drop_thr, a.drop_scale);
   cf4 acc[RMAX];
   float m[RMAX], den[RMAX];
 #pragma unroll
@@ -659,7 +685,10 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_fwd_center_sf_tiled_kernel
         for (int j0 = t0; j0 < t1; j0 += B) {
           float yn[B];
           int tn[B];
-          load(j0 + B, yn, tn);
+          // (DROP at RMAX 4: no prefetch — the next batch's 8 registers are what the mask's arithmetic takes;
+          // the batch, its order and so every bit of max / denominator / logits stay the plain instance's)
+          constexpr bool PREFETCH = !(DROP && RMAX > 2 && B > 2);
+          if constexpr (PREFETCH) load(j0 + B, yn, tn);
           cf4 sv[B];
           float lg[B];
           float mb = -INFINITY;
@@ -677,6 +706,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_fwd_center_sf_tiled_kernel
             yl[5] = dpp_mov<0x155>(yv[uu]);
             yl[6] = dpp_mov<0x156>(yv[uu]);
             cf4 s4 = bias4;
+            if constexpr (DROP && RMAX > 2 && B > 2) s4 = ld4(a.bias + c0);  // (re-read: four registers fewer held)
 #pragma unroll
             for (int l = 0; l < kSfL; ++l) s4 += yl[l] * P[(jr * kSfL + l) * 32 + l32];
             sv[uu] = s4;
@@ -701,13 +731,20 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_fwd_center_sf_tiled_kernel
             const float p = lg[uu] == -INFINITY ? 0.f : expf(lg[uu] - m_new);
             const cf4 vr = VE[((j < t1 ? j : t1 - 1) - t0) * 32 + l32];
             den[r] += p;
-            acc[r] += p * (vr * sv[uu]);
+            if constexpr (DROP)
+              acc[r] += (p * (drop_keep(dkey, tt[uu], head, a.H) ? dkey.scale : 0.f)) * (vr * sv[uu]);
+            else
+              acc[r] += p * (vr * sv[uu]);
           }
           m[r] = m_new;
+          if constexpr (PREFETCH) {
 #pragma unroll
-          for (int uu = 0; uu < B; ++uu) {
-            yv[uu] = yn[uu];
-            tt[uu] = tn[uu];
+            for (int uu = 0; uu < B; ++uu) {
+              yv[uu] = yn[uu];
+              tt[uu] = tn[uu];
+            }
+          } else {
+            load(j0 + B, yv, tt);
           }
         }
       }
@@ -738,7 +775,7 @@ constexpr size_t fwd_sf_tiled_lds() {
   return static_cast<size_t>(kTileRows) * ((2 + kSfL) * kCD + kSfK) * 4 + 2 * X2G_CENTER_MAX_DEGREE * 4;
 }
 
-template <int LPH>
+template <int LPH, bool DROP>
 int fwd_sf_tiled_launch(const FwdSfArgs& a, bool edge, int max_degree, hipStream_t st) {
   // batches of 4 sources: with 8 the RMAX destinations' state spills (4-6 VGPRs at RMAX 2, 15-17 at 4)
   constexpr int W = 8, B = 4;
@@ -754,18 +791,33 @@ int fwd_sf_tiled_launch(const FwdSfArgs& a, bool edge, int max_degree, hipStream
   constexpr int NO = 2 * W;
   // STORE: logits / S rows / P rows for a backward or the attention weights (inference stores none: no store
   // in the pipelined batch loop, whose load waits then stay counted)
+  // (DROP: the storing instance whatever is stored: its stores are guarded by their pointers)
   const bool store = a.alpha || a.sp || a.pp;
   auto pick = [&](auto rmax) -> int {
     constexpr int R = decltype(rmax)::value;
-    if (store)
-      return edge ? go(attn_fwd_center_sf_tiled_kernel<LPH, W, B, true, R, true>)
-                  : go(attn_fwd_center_sf_tiled_kernel<LPH, W, B, false, R, true>);
-    return edge ? go(attn_fwd_center_sf_tiled_kernel<LPH, W, B, true, R, false>)
-                : go(attn_fwd_center_sf_tiled_kernel<LPH, W, B, false, R, false>);
+    if constexpr (DROP) {
+      // the dropout instances must not spill: RMAX 8 has no instance (21 VGPRs spilled even at batches of 1:
+      // degrees above 64 are refused)
+      static_assert(R <= 4, "no RMAX 8 dropout instance");
+      // (32 heads, no edge term, RMAX 4: 4 VGPRs spilled at batches of 4, none at 2 — the one dropout instance
+      // whose batches, and so its denominators' rounding, are not the plain instance's)
+      constexpr int BN = LPH == 1 && R > 2 ? 2 : B;
+      return edge ? go(attn_fwd_center_sf_tiled_kernel<LPH, W, B, true, R, true, true>)
+                  : go(attn_fwd_center_sf_tiled_kernel<LPH, W, BN, false, R, true, true>);
+    } else {
+      if (store)
+        return edge ? go(attn_fwd_center_sf_tiled_kernel<LPH, W, B, true, R, true, false>)
+                    : go(attn_fwd_center_sf_tiled_kernel<LPH, W, B, false, R, true, false>);
+      return edge ? go(attn_fwd_center_sf_tiled_kernel<LPH, W, B, true, R, false, false>)
+                  : go(attn_fwd_center_sf_tiled_kernel<LPH, W, B, false, R, false, false>);
+    }
   };
   if (max_degree <= 2 * NO) return pick(std::integral_constant<int, 2>{});
   if (max_degree <= 4 * NO) return pick(std::integral_constant<int, 4>{});
-  return pick(std::integral_constant<int, 8>{});
+  if constexpr (DROP)
+    return X2G_EUNSUPPORTED;
+  else
+    return pick(std::integral_constant<int, 8>{});
 }
 
 template <int LPH>
@@ -814,6 +866,10 @@ struct BwdCenterArgs {
   float inv_sqrt_c;
   float sqrt_c;  // FACT: the logits are recomputed as the forward formed them (q . (k + e) / sqrt C)
   float *dq, *dk, *dv, *gfold, *d_edge, *gw;  // gw: [T, H] (g, a) pairs of scratch
+  // the DROP instances' (attention dropout: common.hpp drop_key, include/x2g_staged.h)
+  const int64_t* drop_key;
+  uint32_t drop_salt, drop_thr;
+  float drop_scale;
 };
 
 template <int H>
@@ -823,8 +879,15 @@ __host__ __device__ constexpr size_t bwd_center_lds(int n) {
          + static_cast<size_t>(n) * 4 * 2;     // TB, DI
 }
 
-template <int LPH, int WAVES, int B, bool EDGE, bool FACT>
+// DROP (attention dropout, FACT only): with r_t the triplet's keep scale per head (regenerated from the key,
+// the forward's), g_t = r_t sum go_i (v_j + e) S_t and dv_j += a_t r_t go_i S_t in pass 1, and
+// G_j[l] += a_t r_t go_i (v_j + e) Y_l(t) in pass 2.  The scratch pair is (g_t r_t, +-a_t): a_t >= 0, and its sign
+// bit says "dropped", so pass 2 needs neither the mask's arithmetic nor a register for it (it keeps its 8
+// triplets per round trip without spills; regenerating the bit there spilled 4-6 VGPRs); rho and the w terms
+// read |a_t| (a source modifier, no instruction).
+template <int LPH, int WAVES, int B, bool EDGE, bool FACT, bool DROP>
 __global__ void __launch_bounds__(64 * WAVES, 4) attn_bwd_center_kernel(const BwdCenterArgs a) {
+  static_assert(FACT || !DROP, "the dropout instances are the P-row ones");
   constexpr int H = 32 / LPH;
   extern __shared__ cf4 lds[];
   const int64_t b = a.order ? static_cast<int64_t>(a.order[blockIdx.x]) : static_cast<int64_t>(blockIdx.x);
@@ -837,6 +900,8 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_bwd_center_kernel(const Bw
   const int head = l32 / LPH;
   const bool leader = (l32 % LPH) == 0;
   const int c0 = 4 * l32;
+  DropKey dkey{};
+  if constexpr (DROP) dkey = drop_key(a.drop_key, a.drop_salt, a.drop_thr, a.drop_scale);
   if (n <= 0) {  // an atom without edges: its element-table gradient row is zero
     if (a.d_edge && tid < 32) st4(a.d_edge + b * kCD + c0, cf4{0.f, 0.f, 0.f, 0.f});
     return;
@@ -1040,11 +1105,20 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_bwd_center_kernel(const Bw
             gp = fmaf(gu[2], st[2], gp);
             gp = fmaf(gu[3], st[3], gp);
             const float g = head_sum<LPH>(gp);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned,
-                                                                     make_float2(g, at)),
-                                                  ag_r, (ok && leader) ? (tt[u] * H + head) * 8 : static_cast<int>(0x80000000u),
-                                                  0, 0);
-            dv += at * (go * st);
+            if constexpr (DROP) {
+              const float rk = drop_keep(dkey, tt[u], head, H) ? dkey.scale : 0.f;
+              __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned,
+                                                                       make_float2(g * rk, rk != 0.f ? at : -at)),
+                                                    ag_r, (ok && leader) ? (tt[u] * H + head) * 8 : static_cast<int>(0x80000000u),
+                                                    0, 0);
+              dv += (at * rk) * (go * st);
+            } else {
+              __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned,
+                                                                       make_float2(g, at)),
+                                                    ag_r, (ok && leader) ? (tt[u] * H + head) * 8 : static_cast<int>(0x80000000u),
+                                                    0, 0);
+              dv += at * (go * st);
+            }
           }
 #pragma unroll
           for (int u = 0; u < BB; ++u) {
@@ -1077,7 +1151,12 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_bwd_center_kernel(const Bw
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u)
-        if (p0 + u < nt) rho = fmaf(at[u], g[u], rho);
+        if (p0 + u < nt) {
+          if constexpr (DROP)
+            rho = fmaf(fabsf(at[u]), g[u], rho);
+          else
+            rho = fmaf(at[u], g[u], rho);
+        }
     }
     if (leader) RHO[i * H + head] = rho;
   }
@@ -1111,12 +1190,16 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_bwd_center_kernel(const Bw
       for (int u = 0; u < BB; ++u) {
         const int x = x0 + u < n ? x0 + u : n - 1;
         const bool ok = x0 + u < n && x != o;
-        const float as = ok ? ats[u] : 0.f, ad = ok ? atd[u] : 0.f;
+        const float as = ok ? (DROP ? fabsf(ats[u]) : ats[u]) : 0.f, ad = ok ? (DROP ? fabsf(atd[u]) : atd[u]) : 0.f;
         const float ws = as * (gs[u] - RHO[x * H + head]) * a.inv_sqrt_c;
         dk += ws * QI[x * 32 + l32];
         const float wd = ad * (gd[u] - rho_o) * a.inv_sqrt_c;
         dq += wd * KE[x * 32 + l32];
-        const cf4 ds = (GO[x * 32 + l32] * ue) * as;
+        cf4 ds;
+        if constexpr (DROP)
+          ds = (GO[x * 32 + l32] * ue) * (as * (__float_as_int(ats[u]) < 0 ? 0.f : dkey.scale));
+        else
+          ds = (GO[x * 32 + l32] * ue) * as;
         float yl[8];
         yl[0] = dpp_mov<0x150>(yv[u]);
         yl[1] = dpp_mov<0x151>(yv[u]);
@@ -1152,7 +1235,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) attn_bwd_center_kernel(const Bw
   }
 }
 
-template <int LPH>
+template <int LPH, bool DROP>
 int bwd_center_launch(const BwdCenterArgs& a, bool edge, int max_degree, hipStream_t st) {
   constexpr int W = 4, B = 8;
   constexpr int H = 32 / LPH;
@@ -1169,8 +1252,29 @@ int bwd_center_launch(const BwdCenterArgs& a, bool edge, int max_degree, hipStre
     return last_launch_status();
   };
   if (a.pp)
-    return edge ? go(attn_bwd_center_kernel<LPH, W, B, true, true>) : go(attn_bwd_center_kernel<LPH, W, B, false, true>);
-  return edge ? go(attn_bwd_center_kernel<LPH, W, B, true, false>) : go(attn_bwd_center_kernel<LPH, W, B, false, false>);
+    return edge ? go(attn_bwd_center_kernel<LPH, W, B, true, true, DROP>)
+                : go(attn_bwd_center_kernel<LPH, W, B, false, true, DROP>);
+  if constexpr (!DROP)
+    return edge ? go(attn_bwd_center_kernel<LPH, W, B, true, false, false>)
+                : go(attn_bwd_center_kernel<LPH, W, B, false, false, false>);
+  return X2G_EUNSUPPORTED;
+}
+
+// attention dropout as the staged entry points take it (include/x2g_staged.h); NULL: the plain entry
+struct DropIn {
+  float p;
+  const int64_t* key;
+  uint32_t salt;
+};
+
+// the checks every drop entry adds to its parent's, and the kernels' arguments
+template <class Args>
+int drop_args(const DropIn* drop, Args* a) {
+  if (!drop) return X2G_OK;
+  if (!drop->key || !drop_params(drop->p, &a->drop_thr, &a->drop_scale)) return X2G_EINVAL;
+  a->drop_key = drop->key;
+  a->drop_salt = drop->salt;
+  return X2G_OK;
 }
 
 }  // namespace
@@ -1184,7 +1288,7 @@ X2G_API size_t x2g_sbf_attention_bwd_center_lds(int32_t max_degree, int32_t head
   return static_cast<size_t>(n) * 4 * kCD * 4 + static_cast<size_t>(n) * heads * 12 + static_cast<size_t>(n) * 8;
 }
 
-X2G_API int x2g_sbf_attention_bwd_center(const float* q, const float* k, const float* v, const float* edge,
+static int bwd_center_entry(const float* q, const float* k, const float* v, const float* edge,
                                          const int32_t* src_row, int edge_mode, const float* sbfproj,
                                          const float* sbf_p, const float* b_sbf,
                                          const float* sph_y, const int32_t* atom_rowptr, const int32_t* edge_rev,
@@ -1193,7 +1297,7 @@ X2G_API int x2g_sbf_attention_bwd_center(const float* q, const float* k, const f
                                          const float* seg_den, const float* dout, int64_t num_atoms,
                                          int32_t max_degree, int64_t num_edges, int64_t num_triplets, int32_t heads,
                                          int32_t channels, float* dq, float* dk, float* dv, float* radial_grad,
-                                         float* d_edge_atom, float* g_work, void* stream) {
+                                         float* d_edge_atom, float* g_work, void* stream, const DropIn* drop) {
   if (num_atoms < 0 || num_edges < 0 || num_triplets < 0 || heads <= 0 || channels <= 0) return X2G_EINVAL;
   if (edge_mode != X2G_EDGE_NONE && edge_mode != X2G_EDGE_PER_DST) return X2G_EUNSUPPORTED;
   if (heads * channels != kCD || channels % 4 || max_degree < 0 || max_degree > X2G_CENTER_MAX_DEGREE)
@@ -1202,8 +1306,11 @@ X2G_API int x2g_sbf_attention_bwd_center(const float* q, const float* k, const f
   // 32-bit buffer offsets: the S rows (T x 512 B), or with P rows the (g, a) scratch (T x H x 8 B, the
   // largest T-row array then: logits T x H x 4, Y rows T x 32)
   if (num_triplets * (sbf_p ? int64_t(heads) * 8 : int64_t(kCD) * 4) >= (int64_t(1) << 31)) return X2G_EUNSUPPORTED;
+  BwdCenterArgs a{};
+  if (const int rc = drop_args(drop, &a)) return rc;
   if (num_atoms == 0) return X2G_OK;
   if (!sbfproj == !sbf_p || (sbf_p && !b_sbf)) return X2G_EINVAL;  // S rows, or the P rows and the bias
+  if (drop && !sbf_p) return X2G_EUNSUPPORTED;  // dropout: the P-row form only
   if (num_edges > 0 && (!q || !k || !v || !sph_y || !atom_rowptr || !edge_rev || !rev_trip ||
                         (!alpha_raw && !sbf_p) || !seg_max || !seg_den || !dout || !dq || !dk || !dv ||
                         !radial_grad || (num_triplets > 0 && !g_work)))
@@ -1214,7 +1321,6 @@ X2G_API int x2g_sbf_attention_bwd_center(const float* q, const float* k, const f
   if (!al(q, 16) || !al(k, 16) || !al(v, 16) || !al(edge, 16) || !al(sbfproj, 16) || !al(dout, 16) || !al(dq, 16) ||
       !al(dk, 16) || !al(dv, 16) || !al(radial_grad, 16) || !al(d_edge_atom, 16) || !al(sbf_p, 16) || !al(b_sbf, 16))
     return X2G_EUNSUPPORTED;
-  BwdCenterArgs a{};
   a.pp = sbf_p; a.bias = b_sbf;
   a.q = q; a.k = k; a.v = v; a.edge = edge; a.src_row = src_row; a.sp = sbfproj; a.alpha = alpha_raw;
   a.smax = seg_max; a.sden = seg_den; a.dout = dout; a.y = sph_y; a.atom_rowptr = atom_rowptr; a.edge_rev = edge_rev;
@@ -1226,12 +1332,45 @@ X2G_API int x2g_sbf_attention_bwd_center(const float* q, const float* k, const f
   const bool edge_on = edge_mode == X2G_EDGE_PER_DST;
   hipStream_t st = as_stream(stream);
   switch (channels / 4) {
-    case 1: return bwd_center_launch<1>(a, edge_on, md, st);
-    case 2: return bwd_center_launch<2>(a, edge_on, md, st);
-    case 4: return bwd_center_launch<4>(a, edge_on, md, st);
-    case 8: return bwd_center_launch<8>(a, edge_on, md, st);
+    case 1: return drop ? bwd_center_launch<1, true>(a, edge_on, md, st) : bwd_center_launch<1, false>(a, edge_on, md, st);
+    case 2: return drop ? bwd_center_launch<2, true>(a, edge_on, md, st) : bwd_center_launch<2, false>(a, edge_on, md, st);
+    case 4: return drop ? bwd_center_launch<4, true>(a, edge_on, md, st) : bwd_center_launch<4, false>(a, edge_on, md, st);
+    case 8: return drop ? bwd_center_launch<8, true>(a, edge_on, md, st) : bwd_center_launch<8, false>(a, edge_on, md, st);
     default: return X2G_EUNSUPPORTED;
   }
+}
+
+X2G_API int x2g_sbf_attention_bwd_center(const float* q, const float* k, const float* v, const float* edge,
+                                         const int32_t* src_row, int edge_mode, const float* sbfproj,
+                                         const float* sbf_p, const float* b_sbf,
+                                         const float* sph_y, const int32_t* atom_rowptr, const int32_t* edge_rev,
+                                         const int32_t* rev_trip, const int32_t* atom_order, const float* alpha_raw,
+                                         const float* seg_max,
+                                         const float* seg_den, const float* dout, int64_t num_atoms,
+                                         int32_t max_degree, int64_t num_edges, int64_t num_triplets, int32_t heads,
+                                         int32_t channels, float* dq, float* dk, float* dv, float* radial_grad,
+                                         float* d_edge_atom, float* g_work, void* stream) {
+  return bwd_center_entry(q, k, v, edge, src_row, edge_mode, sbfproj, sbf_p, b_sbf, sph_y, atom_rowptr, edge_rev,
+                          rev_trip, atom_order, alpha_raw, seg_max, seg_den, dout, num_atoms, max_degree, num_edges,
+                          num_triplets, heads, channels, dq, dk, dv, radial_grad, d_edge_atom, g_work, stream,
+                          nullptr);
+}
+
+X2G_API int x2g_sbf_attention_bwd_center_drop(const float* q, const float* k, const float* v, const float* edge,
+                                              const int32_t* src_row, int edge_mode, const float* sbfproj,
+                                              const float* sbf_p, const float* b_sbf, const float* sph_y,
+                                              const int32_t* atom_rowptr, const int32_t* edge_rev,
+                                              const int32_t* rev_trip, const int32_t* atom_order,
+                                              const float* alpha_raw, const float* seg_max, const float* seg_den,
+                                              const float* dout, int64_t num_atoms, int32_t max_degree,
+                                              int64_t num_edges, int64_t num_triplets, int32_t heads,
+                                              int32_t channels, float* dq, float* dk, float* dv, float* radial_grad,
+                                              float* d_edge_atom, float* g_work, void* stream, float drop_p,
+                                              const int64_t* drop_key, uint32_t salt) {
+  const DropIn drop{drop_p, drop_key, salt};
+  return bwd_center_entry(q, k, v, edge, src_row, edge_mode, sbfproj, sbf_p, b_sbf, sph_y, atom_rowptr, edge_rev,
+                          rev_trip, atom_order, alpha_raw, seg_max, seg_den, dout, num_atoms, max_degree, num_edges,
+                          num_triplets, heads, channels, dq, dk, dv, radial_grad, d_edge_atom, g_work, stream, &drop);
 }
 
 X2G_API int x2g_sbf_attention_fwd_center(const float* q, const float* k, const float* v, const float* skip,
@@ -1276,7 +1415,7 @@ X2G_API int x2g_sbf_attention_fwd_center(const float* q, const float* k, const f
   }
 }
 
-X2G_API int x2g_sbf_attention_fwd_center_sf(const float* q, const float* k, const float* v, const float* skip,
+static int fwd_center_sf_entry(const float* q, const float* k, const float* v, const float* skip,
                                             const float* edge, const int32_t* src_row, int edge_mode,
                                             const float* radial, const float* sph_y, const float* w_sbf,
                                             const float* b_sbf, const int32_t* atom_rowptr, const int32_t* edge_rev,
@@ -1286,13 +1425,15 @@ X2G_API int x2g_sbf_attention_fwd_center_sf(const float* q, const float* k, cons
                                             int32_t max_rows, int64_t num_edges, int64_t num_triplets, int32_t heads,
                                             int32_t channels, float* out, float* alpha_raw, float* seg_max,
                                             float* seg_den, float* row_stats, float* sbfproj_out, float* sbf_p_out,
-                                            void* stream) {
+                                            void* stream, const DropIn* drop) {
   if (n_units < 0 || unit0 < 0 || num_edges < 0 || num_triplets < 0 || heads <= 0 || channels <= 0)
     return X2G_EINVAL;
   if (edge_mode != X2G_EDGE_NONE && edge_mode != X2G_EDGE_PER_DST) return X2G_EUNSUPPORTED;
   if (heads * channels != kCD || channels % 4 || max_rows < 0 || max_rows > X2G_CENTER_MAX_DEGREE ||
       fwd_sf_lds(max_rows > 0 ? max_rows : 1) > 160 * 1024)
     return X2G_EUNSUPPORTED;
+  FwdSfArgs a{};
+  if (const int rc = drop_args(drop, &a)) return rc;
   if (n_units == 0 || num_edges == 0) return X2G_OK;
   if (!q || !k || !v || !skip || !radial || !sph_y || !w_sbf || !b_sbf || !atom_rowptr || !edge_rev || !rev_trip ||
       !out || !seg_max || !seg_den || (pack_ptr && !atom_order))
@@ -1303,7 +1444,6 @@ X2G_API int x2g_sbf_attention_fwd_center_sf(const float* q, const float* k, cons
   if (!al(q, 16) || !al(k, 16) || !al(v, 16) || !al(skip, 16) || !al(edge, 16) || !al(out, 16) || !al(b_sbf, 16) ||
       !al(sbfproj_out, 16) || !al(sbf_p_out, 16) || !al(row_stats, 8) || !al(atom_info, 16))
     return X2G_EUNSUPPORTED;
-  FwdSfArgs a{};
   a.info = reinterpret_cast<const int4*>(atom_info);
   a.pp = sbf_p_out;
   a.q = q; a.k = k; a.v = v; a.skip = skip; a.edge = edge; a.src_row = src_row; a.radial = radial; a.y = sph_y;
@@ -1316,17 +1456,53 @@ X2G_API int x2g_sbf_attention_fwd_center_sf(const float* q, const float* k, cons
   const bool edge_on = edge_mode == X2G_EDGE_PER_DST;
   hipStream_t st = as_stream(stream);
   switch (channels / 4) {
-    case 1: return fwd_sf_launch<1>(a, edge_on, st);
-    case 2: return fwd_sf_launch<2>(a, edge_on, st);
-    case 4: return fwd_sf_launch<4>(a, edge_on, st);
-    case 8: return fwd_sf_launch<8>(a, edge_on, st);
+    case 1: return drop ? fwd_sf_launch<1, true>(a, edge_on, st) : fwd_sf_launch<1, false>(a, edge_on, st);
+    case 2: return drop ? fwd_sf_launch<2, true>(a, edge_on, st) : fwd_sf_launch<2, false>(a, edge_on, st);
+    case 4: return drop ? fwd_sf_launch<4, true>(a, edge_on, st) : fwd_sf_launch<4, false>(a, edge_on, st);
+    case 8: return drop ? fwd_sf_launch<8, true>(a, edge_on, st) : fwd_sf_launch<8, false>(a, edge_on, st);
     default: return X2G_EUNSUPPORTED;
   }
 }
 
+X2G_API int x2g_sbf_attention_fwd_center_sf(const float* q, const float* k, const float* v, const float* skip,
+                                            const float* edge, const int32_t* src_row, int edge_mode,
+                                            const float* radial, const float* sph_y, const float* w_sbf,
+                                            const float* b_sbf, const int32_t* atom_rowptr, const int32_t* edge_rev,
+                                            const int32_t* rev_trip, const int32_t* atom_order,
+                                            const int32_t* pack_ptr, const int32_t* atom_info, int64_t unit0,
+                                            int64_t n_units,
+                                            int32_t max_rows, int64_t num_edges, int64_t num_triplets, int32_t heads,
+                                            int32_t channels, float* out, float* alpha_raw, float* seg_max,
+                                            float* seg_den, float* row_stats, float* sbfproj_out, float* sbf_p_out,
+                                            void* stream) {
+  return fwd_center_sf_entry(q, k, v, skip, edge, src_row, edge_mode, radial, sph_y, w_sbf, b_sbf, atom_rowptr,
+                             edge_rev, rev_trip, atom_order, pack_ptr, atom_info, unit0, n_units, max_rows, num_edges,
+                             num_triplets, heads, channels, out, alpha_raw, seg_max, seg_den, row_stats, sbfproj_out,
+                             sbf_p_out, stream, nullptr);
+}
+
+X2G_API int x2g_sbf_attention_fwd_center_sf_drop(const float* q, const float* k, const float* v, const float* skip,
+                                                 const float* edge, const int32_t* src_row, int edge_mode,
+                                                 const float* radial, const float* sph_y, const float* w_sbf,
+                                                 const float* b_sbf, const int32_t* atom_rowptr,
+                                                 const int32_t* edge_rev, const int32_t* rev_trip,
+                                                 const int32_t* atom_order, const int32_t* pack_ptr,
+                                                 const int32_t* atom_info, int64_t unit0, int64_t n_units,
+                                                 int32_t max_rows, int64_t num_edges, int64_t num_triplets,
+                                                 int32_t heads, int32_t channels, float* out, float* alpha_raw,
+                                                 float* seg_max, float* seg_den, float* row_stats,
+                                                 float* sbfproj_out, float* sbf_p_out, void* stream, float drop_p,
+                                                 const int64_t* drop_key, uint32_t salt) {
+  const DropIn drop{drop_p, drop_key, salt};
+  return fwd_center_sf_entry(q, k, v, skip, edge, src_row, edge_mode, radial, sph_y, w_sbf, b_sbf, atom_rowptr,
+                             edge_rev, rev_trip, atom_order, pack_ptr, atom_info, unit0, n_units, max_rows, num_edges,
+                             num_triplets, heads, channels, out, alpha_raw, seg_max, seg_den, row_stats, sbfproj_out,
+                             sbf_p_out, stream, &drop);
+}
+
 X2G_API size_t x2g_sbf_attention_fwd_center_sf_tiled_lds(void) { return fwd_sf_tiled_lds(); }
 
-X2G_API int x2g_sbf_attention_fwd_center_sf_tiled(const float* q, const float* k, const float* v, const float* skip,
+static int fwd_center_sf_tiled_entry(const float* q, const float* k, const float* v, const float* skip,
                                                   const float* edge, const int32_t* src_row, int edge_mode,
                                                   const float* radial, const float* sph_y, const float* w_sbf,
                                                   const float* b_sbf, const int32_t* atom_rowptr,
@@ -1337,12 +1513,16 @@ X2G_API int x2g_sbf_attention_fwd_center_sf_tiled(const float* q, const float* k
                                                   int64_t num_triplets,
                                                   int32_t heads, int32_t channels, float* out, float* alpha_raw,
                                                   float* seg_max, float* seg_den, float* row_stats,
-                                                  float* sbfproj_out, float* sbf_p_out, void* stream) {
+                                                  float* sbfproj_out, float* sbf_p_out, void* stream,
+                                                  const DropIn* drop) {
   if (n_units < 0 || unit0 < 0 || num_edges < 0 || num_triplets < 0 || heads <= 0 || channels <= 0)
     return X2G_EINVAL;
   if (edge_mode != X2G_EDGE_NONE && edge_mode != X2G_EDGE_PER_DST) return X2G_EUNSUPPORTED;
   if (heads * channels != kCD || channels % 4 || max_degree < 0 || max_degree > X2G_CENTER_MAX_DEGREE)
     return X2G_EUNSUPPORTED;
+  if (drop && max_degree > 64) return X2G_EUNSUPPORTED;  // no RMAX 8 dropout instance (fwd_sf_tiled_launch)
+  FwdSfArgs a{};
+  if (const int rc = drop_args(drop, &a)) return rc;
   if (n_units == 0 || num_edges == 0) return X2G_OK;
   if (!q || !k || !v || !skip || !radial || !sph_y || !w_sbf || !b_sbf || !atom_rowptr || !edge_rev || !rev_trip ||
       !out || !seg_max || !seg_den || (pack_ptr && !atom_order))
@@ -1352,7 +1532,6 @@ X2G_API int x2g_sbf_attention_fwd_center_sf_tiled(const float* q, const float* k
   if (!al(q, 16) || !al(k, 16) || !al(v, 16) || !al(skip, 16) || !al(edge, 16) || !al(out, 16) || !al(b_sbf, 16) ||
       !al(sbfproj_out, 16) || !al(sbf_p_out, 16) || !al(row_stats, 8) || !al(atom_info, 16))
     return X2G_EUNSUPPORTED;
-  FwdSfArgs a{};
   a.info = reinterpret_cast<const int4*>(atom_info);
   a.pp = sbf_p_out;
   a.q = q; a.k = k; a.v = v; a.skip = skip; a.edge = edge; a.src_row = src_row; a.radial = radial; a.y = sph_y;
@@ -1366,10 +1545,74 @@ X2G_API int x2g_sbf_attention_fwd_center_sf_tiled(const float* q, const float* k
   const int md = max_degree > 0 ? max_degree : 1;
   hipStream_t st = as_stream(stream);
   switch (channels / 4) {
-    case 1: return fwd_sf_tiled_launch<1>(a, edge_on, md, st);
-    case 2: return fwd_sf_tiled_launch<2>(a, edge_on, md, st);
-    case 4: return fwd_sf_tiled_launch<4>(a, edge_on, md, st);
-    case 8: return fwd_sf_tiled_launch<8>(a, edge_on, md, st);
+    case 1: return drop ? fwd_sf_tiled_launch<1, true>(a, edge_on, md, st) : fwd_sf_tiled_launch<1, false>(a, edge_on, md, st);
+    case 2: return drop ? fwd_sf_tiled_launch<2, true>(a, edge_on, md, st) : fwd_sf_tiled_launch<2, false>(a, edge_on, md, st);
+    case 4: return drop ? fwd_sf_tiled_launch<4, true>(a, edge_on, md, st) : fwd_sf_tiled_launch<4, false>(a, edge_on, md, st);
+    case 8: return drop ? fwd_sf_tiled_launch<8, true>(a, edge_on, md, st) : fwd_sf_tiled_launch<8, false>(a, edge_on, md, st);
     default: return X2G_EUNSUPPORTED;
   }
+}
+
+X2G_API int x2g_sbf_attention_fwd_center_sf_tiled(const float* q, const float* k, const float* v, const float* skip,
+                                                  const float* edge, const int32_t* src_row, int edge_mode,
+                                                  const float* radial, const float* sph_y, const float* w_sbf,
+                                                  const float* b_sbf, const int32_t* atom_rowptr,
+                                                  const int32_t* edge_rev, const int32_t* rev_trip,
+                                                  const int32_t* atom_order, const int32_t* pack_ptr,
+                                                  const int32_t* atom_info, int64_t unit0, int64_t n_units,
+                                                  int32_t max_degree, int32_t skip_rows, int64_t num_edges,
+                                                  int64_t num_triplets,
+                                                  int32_t heads, int32_t channels, float* out, float* alpha_raw,
+                                                  float* seg_max, float* seg_den, float* row_stats,
+                                                  float* sbfproj_out, float* sbf_p_out, void* stream) {
+  return fwd_center_sf_tiled_entry(q, k, v, skip, edge, src_row, edge_mode, radial, sph_y, w_sbf, b_sbf, atom_rowptr,
+                                   edge_rev, rev_trip, atom_order, pack_ptr, atom_info, unit0, n_units, max_degree,
+                                   skip_rows, num_edges, num_triplets, heads, channels, out, alpha_raw, seg_max,
+                                   seg_den, row_stats, sbfproj_out, sbf_p_out, stream, nullptr);
+}
+
+X2G_API int x2g_sbf_attention_fwd_center_sf_tiled_drop(
+    const float* q, const float* k, const float* v, const float* skip, const float* edge, const int32_t* src_row,
+    int edge_mode, const float* radial, const float* sph_y, const float* w_sbf, const float* b_sbf,
+    const int32_t* atom_rowptr, const int32_t* edge_rev, const int32_t* rev_trip, const int32_t* atom_order,
+    const int32_t* pack_ptr, const int32_t* atom_info, int64_t unit0, int64_t n_units, int32_t max_degree,
+    int32_t skip_rows, int64_t num_edges, int64_t num_triplets, int32_t heads, int32_t channels, float* out,
+    float* alpha_raw, float* seg_max, float* seg_den, float* row_stats, float* sbfproj_out, float* sbf_p_out,
+    void* stream, float drop_p, const int64_t* drop_key, uint32_t salt) {
+  const DropIn drop{drop_p, drop_key, salt};
+  return fwd_center_sf_tiled_entry(q, k, v, skip, edge, src_row, edge_mode, radial, sph_y, w_sbf, b_sbf, atom_rowptr,
+                                   edge_rev, rev_trip, atom_order, pack_ptr, atom_info, unit0, n_units, max_degree,
+                                   skip_rows, num_edges, num_triplets, heads, channels, out, alpha_raw, seg_max,
+                                   seg_den, row_stats, sbfproj_out, sbf_p_out, stream, &drop);
+}
+
+// r [T, H] of the attention dropout's mask: the device statement of include/x2g_staged.h's definition
+namespace x2g {
+namespace {
+__global__ void __launch_bounds__(256) attn_dropout_mask_kernel(int64_t n, int H, const int64_t* key, uint32_t salt,
+                                                                uint32_t thr, float scale, float* r) {
+  const DropKey d = drop_key(key, salt, thr, scale);
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; idx < n; idx += stride) {
+    const int64_t t = idx / H;
+    r[idx] = drop_keep(d, static_cast<uint32_t>(t), static_cast<uint32_t>(idx - t * H), H) ? d.scale : 0.f;
+  }
+}
+}  // namespace
+}  // namespace x2g
+
+X2G_API int x2g_attn_dropout_mask(int64_t T, int H, float drop_p, const int64_t* drop_key, uint32_t salt,
+                                  float* r_out, void* stream) {
+  if (T < 0 || H <= 0) return X2G_EINVAL;
+  uint32_t thr;
+  float scale;
+  if (!drop_key || !drop_params(drop_p, &thr, &scale)) return X2G_EINVAL;
+  if (T * H >= (int64_t(1) << 32)) return X2G_EUNSUPPORTED;  // the counter t H + h is 32 bits wide
+  if (T == 0) return X2G_OK;
+  if (!r_out) return X2G_EINVAL;
+  const int64_t n = T * H;
+  const int64_t blocks = (n + 255) / 256;
+  attn_dropout_mask_kernel<<<static_cast<unsigned>(blocks < 4096 ? blocks : 4096), 256, 0, as_stream(stream)>>>(
+      n, H, drop_key, salt, thr, scale, r_out);
+  return last_launch_status();
 }

@@ -104,6 +104,49 @@ __device__ __forceinline__ float xor_xchg(float v) {
   else return __shfl_xor(v, OFF, kWave);
 }
 
+// Attention dropout's counter-based mask (the definition: include/x2g_staged.h).  Never stored: the forward
+// and the backward regenerate it from (key, salt, triplet row, head).  All arithmetic uint32, wrapping.
+__device__ __forceinline__ uint32_t drop_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
+struct DropKey {
+  uint32_t k0, k1;  // uniform over a launch: formed once per thread
+  uint32_t thr;     // keep = bits >= thr
+  float scale;      // 1 / (1 - p)
+};
+
+// the entry points' part: thr = min(floor(p 2^32 + 0.5), 2^32 - 1) and (float)(1 / (1 - p)), formed in
+// double; false for p outside [0, 1)
+inline bool drop_params(float p, uint32_t* thr, float* scale) {
+  if (!(p >= 0.f && p < 1.f)) return false;
+  const double t = static_cast<double>(static_cast<int64_t>(static_cast<double>(p) * 4294967296.0 + 0.5));
+  *thr = t > 4294967295.0 ? 0xffffffffu : static_cast<uint32_t>(t);
+  *scale = static_cast<float>(1.0 / (1.0 - static_cast<double>(p)));
+  return true;
+}
+
+// key: two int64 words in device memory, (seed, step counter)
+__device__ __forceinline__ DropKey drop_key(const int64_t* key, uint32_t salt, uint32_t thr, float scale) {
+  const uint64_t seed = static_cast<uint64_t>(key[0]), step = static_cast<uint64_t>(key[1]);
+  DropKey d;
+  d.k0 = drop_mix(static_cast<uint32_t>(seed) ^ drop_mix(static_cast<uint32_t>(step) ^ (salt * 0x9E3779B9u)));
+  d.k1 = drop_mix(static_cast<uint32_t>(seed >> 32) + drop_mix(static_cast<uint32_t>(step >> 32) ^ d.k0));
+  d.thr = thr;
+  d.scale = scale;
+  return d;
+}
+
+// whether (triplet row t, head h) of H heads is kept: two mix rounds
+__device__ __forceinline__ bool drop_keep(const DropKey& d, uint32_t t, uint32_t h, uint32_t H) {
+  return drop_mix(drop_mix((t * H + h) ^ d.k0) + d.k1) >= d.thr;
+}
+
 template <int G>
 __device__ __forceinline__ float group_max(float v) {
   if (G >= 2) v = fmaxf(v, xor_xchg<1>(v));

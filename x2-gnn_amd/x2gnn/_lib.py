@@ -21,6 +21,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("X2G_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libx2g.so"))
 HEADER_PATH = os.environ.get("X2G_HEADER",
                              os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "x2g.h"))
+# the staged entry points' header, next to x2g.h: compiled into the same library, outside the recorded ABI
+STAGED_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_staged.h")
 
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int": ctypes.c_int,
             "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
@@ -106,8 +108,22 @@ def _read_header():
         return f.read()
 
 
+def _read_staged():
+    """(signatures, restypes) of x2g_staged.h, read like x2g.h; it declares functions only (no struct, no
+    constant: anything else raises).  Empty when the header is absent (an X2G_HEADER of an earlier tree)."""
+    if not os.path.exists(STAGED_HEADER_PATH):
+        return {}, {}
+    with open(STAGED_HEADER_PATH) as f:
+        sig, res, structs, consts = parse_header(f.read())
+    if structs or consts:
+        raise ValueError(f"x2g_staged.h declares more than functions: {sorted(structs) + sorted(consts)}")
+    return sig, res
+
+
 # name -> argtypes / restype of every function, name -> Structure of every typedef struct, and the #defines
 SIGNATURES, RESTYPES, STRUCTS, CONSTS = parse_header(_read_header())
+# the same for the staged entry points (x2g_staged.h), kept apart: SIGNATURES stays exactly x2g.h's
+STAGED_SIGNATURES, STAGED_RESTYPES = _read_staged()
 
 _lib = None
 
@@ -123,6 +139,12 @@ def load():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = RESTYPES[name]
+        for name, args in STAGED_SIGNATURES.items():
+            # (a library built from an earlier tree, X2G_LIB, has none of them: calling one then raises)
+            fn = getattr(lib, name, None)
+            if fn is not None:
+                fn.argtypes = args
+                fn.restype = STAGED_RESTYPES[name]
         _lib = lib
     return _lib
 

@@ -50,13 +50,14 @@ def _plan_of(data, edge_index_0, atom_batch):
 
 
 class _Trunk(nn.Module):
-    def _build(self, conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads, readout):
+    def _build(self, conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads, readout, attn_dropout=0.0,
+               dropout_seed=0):
         self.in_channels = in_channels
         self.rbf_dim = rbf_dim
         self.edgenn = Sequential(Linear(emb_size, emb_size), SiLU(), Linear(emb_size, emb_size))
         self.convs = ModuleList([
             SBFTransformerConv(in_channels=in_channels, out_channels=int(in_channels / heads), heads=heads,
-                               sbf_dim=sbf_dim * rbf_dim, rbf_dim=rbf_dim, dropout=0, edge_dim=emb_size)
+                               sbf_dim=sbf_dim * rbf_dim, rbf_dim=rbf_dim, dropout=attn_dropout, edge_dim=emb_size)
             for _ in range(conv_layers)])
         self.readouts = ModuleList([readout() for _ in range(conv_layers + 1)])
         self.bf_skip = ModuleList([ResidualLayer(in_channels) for _ in range(conv_layers)])
@@ -66,6 +67,19 @@ class _Trunk(nn.Module):
         self.AF = SiLU()
         self.LayerNorm = LayerNorm(in_channels=in_channels, eps=1e-8, affine=False)
         self.conv_layers = conv_layers
+        # attention dropout's (seed, step): a training forward advances the step on the device (a captured step
+        # on every replay) and hands a copy, with the layer's index as salt, to every conv.  Non-persistent: the
+        # model's state_dict is the same with and without dropout (Trainer.state_dict carries it).
+        self.attn_dropout = float(attn_dropout)
+        self.register_buffer("attn_dropout_state", torch.tensor([int(dropout_seed), 0], dtype=torch.int64),
+                             persistent=False)
+
+    def _dropout_key(self):
+        """This forward's key (None: no dropout — eval, or p = 0 — and the state is not touched)."""
+        if not (self.training and self.attn_dropout > 0):
+            return None
+        self.attn_dropout_state[1] += 1
+        return self.attn_dropout_state.clone()
 
     def edge_table_stages(self):
         """edgenn -> every conv's lin_edge as (Linear, act, parent) stages for ops.table_chain (parent
@@ -119,6 +133,7 @@ class _Trunk(nn.Module):
             out._x2g_fanin = ops.FanIn()
         readout(0, out)
         sbf = data.edge_sbf
+        drop_key = self._dropout_key()
         # (every layer's S projected up front in one launch, x2g_sbf_project_batch, measured 1.2 % slower in
         # the step A/B, profiles/r4ab1_step_ab_sbatch_feat.log: each layer's S written right before its
         # attention is still in the MALL when the attention reads it; projected 3 layers early it is not)
@@ -126,7 +141,8 @@ class _Trunk(nn.Module):
             res0 = out
             out = self.convs[i](sbf=sbf, rbf=data.node_rbf, x=out, edge_index=data._store.get("edge_index"),
                                 edge_attr=edge_attr, line_graph=plan.lg, edge_row=edge_row,
-                                edge_proj=edge_proj[i] if edge_proj is not None else None)
+                                edge_proj=edge_proj[i] if edge_proj is not None else None,
+                                dropout_key=drop_key, dropout_salt=i)
             stats = getattr(out, "_x2g_rowstats", None)
             if stats is not None and self._ln_fusable(out, i):
                 # the LayerNorm runs inside the tail's row chain, from the conv's per-row statistics
@@ -208,10 +224,12 @@ class _Trunk(nn.Module):
 class SBFTransformer(_Trunk):
     """Trunk with per-atom readouts (extensive targets, reference model.py:11-54)."""
 
-    def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8):
+    def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8, attn_dropout=0.0,
+                 dropout_seed=0):
         super().__init__()
         self._build(conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads,
-                    lambda: AtomWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=1))
+                    lambda: AtomWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=1),
+                    attn_dropout=attn_dropout, dropout_seed=dropout_seed)
 
     def forward(self, data, edge_index_0, atom_batch):
         plan = _plan_of(data, edge_index_0, atom_batch)
@@ -238,10 +256,12 @@ class SBFTransformer(_Trunk):
 class SBFTransformerGlobal(_Trunk):
     """Trunk with per-molecule readouts (intensive targets, reference model.py:56-98)."""
 
-    def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8, pool_option="mean"):
+    def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8, pool_option="mean",
+                 attn_dropout=0.0, dropout_seed=0):
         super().__init__()
         self._build(conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads,
-                    lambda: MolWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=1, pool_option=pool_option))
+                    lambda: MolWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=1, pool_option=pool_option),
+                    attn_dropout=attn_dropout, dropout_seed=dropout_seed)
 
     def forward(self, data, edge_index_0, atom_batch):
         plan = _plan_of(data, edge_index_0, atom_batch)

@@ -442,12 +442,48 @@ def center_schedule(atom_rowptr, src_row, num_atoms: int):
     return c_order, p_order, p_ptr, info
 
 
-def _center_launch(launches, common, outs):
+def _center_launch(launches, common, outs, drop=()):
+    """``drop``: (p, key pointer, salt) — the launches take the staged dropout entries (x2g_staged.h)."""
     for entry, u0, n, rows, skip in launches:
+        name = entry + "_drop" if drop else entry
         if entry.endswith("_tiled"):
-            call(entry, *common, u0, n, rows, skip, *outs)
+            call(name, *common, u0, n, rows, skip, *outs, *drop)
         else:
-            call(entry, *common, u0, n, rows, *outs)
+            call(name, *common, u0, n, rows, *outs, *drop)
+
+
+# the source-tiled forward's dropout instances hold at most 4 destinations per owner (x2g_staged.h)
+DROPOUT_TILED_MAX_DEGREE = 64
+
+
+def _dropout_route(lg, edge_mode, edge_row, D, channels, heads, factors, backward):
+    """Attention dropout runs on one route only, the fused center forward and (``backward``) the P-row center
+    backward; anything else raises NotImplementedError naming the condition that failed."""
+    why = None
+    if not (_CENTER and _CENTER_SF and _CENTER_P):
+        why = "the center kernels are switched off (ops._CENTER / _CENTER_SF / _CENTER_P)"
+    elif edge_mode == EDGE_PER_TRIPLET:
+        why = "per-triplet edge_attr (the center kernels take no edge term or one row per destination, edge_row)"
+    elif getattr(lg, "edge_rev", None) is None or lg.max_degree is None:
+        why = "a line graph that is not symmetric (no edge_rev / rev_trip: not built by vertex_to_edge)"
+    elif lg.max_degree > CENTER_MAX_DEGREE:
+        why = f"a degree above CENTER_MAX_DEGREE ({lg.max_degree} > {CENTER_MAX_DEGREE})"
+    elif D != 128 or channels % 4:
+        why = f"heads * channels = {D} (compiled: 128, channels a multiple of 4)"
+    elif lg.max_degree > DROPOUT_TILED_MAX_DEGREE:
+        why = (f"a degree above {DROPOUT_TILED_MAX_DEGREE} ({lg.max_degree}): the source-tiled forward has no "
+               "dropout instance for it")
+    elif not _center_rows(lg, edge_mode, edge_row, D, channels)[0]:
+        why = "edge_row is not the line graph's own destination elements (dst_type)"
+    elif factors is None or factors[1] is None:
+        why = "the sbf factors are absent (sbf is not the line graph's own radial x angular product)"
+    elif not _center_sf_ok(lg, factors, D):
+        why = "a unit beyond the fused center forward's LDS image"
+    elif backward and not _center_bwd_ok(lg, heads):
+        why = ("the P-row center backward does not take this line graph (atom_type absent, T * heads * 8 >= 2^31, or "
+               "the largest block's LDS image above 160 KiB)")
+    if why is not None:
+        raise NotImplementedError(f"attention dropout is compiled for the center kernels only: {why}")
 
 
 # Workgroup packs (data.center_packs) in the fused forward: 16 owners per workgroup keep 90 % instead of
@@ -500,7 +536,7 @@ def _center_rows(lg, edge_mode, edge_row, D, channels):
 class _SBFAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode, edge_row, heads, channels,
-                keep_alpha=True):
+                keep_alpha=True, dropout=None):
         w_param, b_param = w_sbf, b_sbf
         # its gradient is read only by the table chain's backward, which flushes deferred sums first
         pending = getattr(edge, "_x2g_keyed_pending", None)
@@ -514,6 +550,14 @@ class _SBFAttention(torch.autograd.Function):
         dev = q.device
         out = torch.empty(E, D, dtype=torch.float32, device=dev)
         center, src_row = _center_rows(lg, edge_mode, edge_row, D, channels)
+        # attention dropout (p, key int64 [2] on the device, salt): the staged entries, on the one route they
+        # cover; the backward regenerates the mask from the key saved here
+        drop, drop_key = (), None
+        if dropout is not None:
+            _dropout_route(lg, edge_mode, edge_row, D, channels, heads, factors, _keeps(ctx))
+            drop_key = dropout[1]
+            drop = (float(dropout[0]), ptr(drop_key), int(dropout[2]))
+        ctx.dropout = None if dropout is None else (drop[0], drop[2])
         # the P-row center backward (the shipped training path) recomputes the logits from rows it stages
         p_bwd = center and _CENTER_P and _center_sf_ok(lg, factors, D) and _center_bwd_ok(lg, heads)
         # the logits [T, H] are read by the other backwards or for the attention weights; the center forwards
@@ -542,7 +586,7 @@ class _SBFAttention(torch.autograd.Function):
                       ptr(lg.rev_trip), ptr(order), ptr(packs), ptr(info))
             outs = (E, T, heads, channels, ptr(out), ptr(alpha), ptr(smax), ptr(sden), ptr(rstats), ptr(sproj),
                     ptr(sbf_p), stream_ptr())
-            _center_launch(launches, common, outs)
+            _center_launch(launches, common, outs, drop)
         else:
             # S = lin_sbf(sbf) once per layer [T, D], right before this layer's attention (so it is still
             # in the MALL when the attention kernels read its rows: sbf pointer = S, weight pointer NULL)
@@ -562,9 +606,9 @@ class _SBFAttention(torch.autograd.Function):
                      ptr(smax), ptr(sden), *((ptr(rstats),) if rstats is not None else ()), stream_ptr())
         if factors is not None:  # the factorised backward never reads sbf itself
             ctx.save_for_backward(q, k, v, edge, factors[0], factors[1], sproj, alpha, smax, sden, sbf_p,
-                                  b_sbf if sbf_p is not None else None)
+                                  b_sbf if sbf_p is not None else None, drop_key)
         else:
-            ctx.save_for_backward(q, k, v, edge, sbf, None, sproj, alpha, smax, sden, None, None)
+            ctx.save_for_backward(q, k, v, edge, sbf, None, sproj, alpha, smax, sden, None, None, None)
         ctx.fold = factors is not None
         ctx.w_param, ctx.b_param = w_param, b_param
         ctx.lg, ctx.edge_mode, ctx.edge_row, ctx.heads, ctx.channels = lg, edge_mode, edge_row, heads, channels
@@ -578,7 +622,7 @@ class _SBFAttention(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, _da=None, _dm=None, _ds=None, _dr=None):
-        q, k, v, edge, sbf, ylm, sproj, alpha, smax, sden, sbf_p, b_sbf = ctx.saved_tensors
+        q, k, v, edge, sbf, ylm, sproj, alpha, smax, sden, sbf_p, b_sbf, drop_key = ctx.saved_tensors
         lg, mode, heads, channels = ctx.lg, ctx.edge_mode, ctx.heads, ctx.channels
         dout = _f32(dout)
         E, T, D = q.shape[0], lg.T, heads * channels
@@ -588,7 +632,7 @@ class _SBFAttention(torch.autograd.Function):
         dv = torch.empty_like(dq)
         if ctx.fold:  # sbf here is the radial factor rbf_env [E, 42]
             return _SBFAttention._backward_fold(ctx, dout, q, k, v, edge, sbf, ylm, sproj, alpha, smax, sden, dq, dk, dv,
-                                                sbf_p, b_sbf)
+                                                sbf_p, b_sbf, drop_key)
         dlogit = torch.empty(T, heads, dtype=torch.float32, device=dev)
         dproj = torch.empty(T, D, dtype=torch.float32, device=dev)
         if mode == EDGE_PER_TRIPLET:
@@ -613,11 +657,11 @@ class _SBFAttention(torch.autograd.Function):
         materialize_sbf(lg, sbf)
         # lin_sbf's dW / db (None where summed into the gradient bucket)
         dw, db = linear_wgrad(dproj, sbf, w_param=ctx.w_param, b_param=ctx.b_param)
-        return dq, dk, dv, dout, d_edge, None, dw, db, None, None, None, None, None, None
+        return dq, dk, dv, dout, d_edge, None, dw, db, None, None, None, None, None, None, None
 
     @staticmethod
     def _backward_fold(ctx, dout, q, k, v, edge, radial, ylm, sproj, alpha, smax, sden, dq, dk, dv, sbf_p=None,
-                       b_sbf=None):
+                       b_sbf=None, drop_key=None):
         lg, mode, heads, channels = ctx.lg, ctx.edge_mode, ctx.heads, ctx.channels
         E, T, D = q.shape[0], lg.T, heads * channels
         dev = q.device
@@ -634,10 +678,13 @@ class _SBFAttention(torch.autograd.Function):
             want_edge = mode == EDGE_PER_DST and ctx.needs_input_grad[4]
             d_edge = torch.empty(lg.N, D, dtype=torch.float32, device=dev) if want_edge else None
             g_work = torch.empty(2, T, heads, dtype=torch.float32, device=dev)
-            call("x2g_sbf_attention_bwd_center", ptr(q), ptr(k), ptr(v), ptr(edge), ptr(src_row), mode, ptr(sproj),
+            # (with dropout: the forward's p, salt and key — the mask is regenerated, never stored)
+            drop = () if ctx.dropout is None else (ctx.dropout[0], ptr(drop_key), ctx.dropout[1])
+            call("x2g_sbf_attention_bwd_center_drop" if drop else "x2g_sbf_attention_bwd_center", ptr(q), ptr(k),
+                 ptr(v), ptr(edge), ptr(src_row), mode, ptr(sproj),
                  ptr(sbf_p), ptr(b_sbf), ptr(ylm), ptr(lg.atom_rowptr), ptr(lg.edge_rev), ptr(lg.rev_trip), ptr(lg.center_order),
                  ptr(alpha), ptr(smax), ptr(sden), ptr(dout), lg.N, lg.max_degree, E, T, heads, channels, ptr(dq),
-                 ptr(dk), ptr(dv), ptr(gfold), ptr(d_edge), ptr(g_work), st)
+                 ptr(dk), ptr(dv), ptr(gfold), ptr(d_edge), ptr(g_work), st, *drop)
             key = lg.atom_type  # d_edge per center atom: summed by the atoms' elements
         else:
             d_edge = torch.empty(E, D, dtype=torch.float32, device=dev) if mode == EDGE_PER_DST else None
@@ -662,7 +709,7 @@ class _SBFAttention(torch.autograd.Function):
                 d_edge = keyed_row_sum(d_edge, key, ctx.edge_shape[0])
         # lin_sbf's dW / db (None where summed into the gradient bucket)
         dw, db = sbf_radial_wgrad(gfold, radial, ctx.w_param, ctx.b_param)
-        return dq, dk, dv, dout, d_edge, None, dw, db, None, None, None, None, None, None
+        return dq, dk, dv, dout, d_edge, None, dw, db, None, None, None, None, None, None, None
 
 
 def sbf_radial_wgrad(gfold, radial, w_param=None, b_param=None):
@@ -1075,24 +1122,43 @@ def _attention_fwd_tiled(q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode, 
 
 
 def sbf_attention(q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg: LineGraph, heads: int, channels: int,
-                  edge_mode: int = EDGE_PER_TRIPLET, edge_row=None, return_attention=False):
+                  edge_mode: int = EDGE_PER_TRIPLET, edge_row=None, return_attention=False, dropout=None):
     """Fused SBFTransformerConv message/softmax/aggregate/skip (see csrc/attention.hip).
 
     With ``return_attention`` also returns the softmax probabilities [T, heads] (the
-    reference's ``return_attention_weights`` alpha)."""
+    reference's ``return_attention_weights`` alpha: the softmax before dropout).
+
+    ``dropout``: None or ``(p, key, salt)`` — attention dropout of probability ``p`` in [0, 1) with the
+    counter-based mask of include/x2g_staged.h: ``key`` an int64 [2] device tensor (seed, step) that the caller
+    does not change in place afterwards (the backward regenerates the forward's mask from it), ``salt`` the
+    layer's index.  It runs on the fused center forward and the P-row center backward only; any other route
+    raises NotImplementedError.  ``p == 0`` is no dropout: today's calls."""
     _need_cuda(q, k, v, skip, sbf)
+    if dropout is not None:
+        p_drop, key, salt = dropout
+        if not 0.0 <= float(p_drop) < 1.0:
+            raise ValueError(f"dropout probability {p_drop} outside [0, 1)")
+        if float(p_drop) == 0.0:
+            dropout = None
+        elif not (torch.is_tensor(key) and key.is_cuda and key.dtype == torch.int64 and key.numel() == 2
+                  and key.is_contiguous()):
+            raise ValueError("dropout key: an int64 [2] device tensor (seed, step)")
+        else:
+            dropout = (float(p_drop), key, int(salt) & 0xFFFFFFFF)
     if edge is None:
         edge_mode = EDGE_NONE
     if edge_row is not None:
         edge_row = _i32(edge_row)
     sf = (_center_rows(lg, edge_mode, edge_row, heads * channels, channels)[0]
           and _center_sf_ok(lg, _sbf_factors(lg, sbf, edge_mode, heads * channels, edge, edge_row), heads * channels))
+    if dropout is not None:  # (its one route is the fused center forward: _SBFAttention raises for another)
+        sf = True
     if not torch.is_grad_enabled() and lg.T > INFER_TILE and q.shape[0] > 0 and not sf:  # (sf: no S at all)
         out, alpha, smax, sden, rstats = _attention_fwd_tiled(q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode,
                                                               edge_row, heads, channels, INFER_TILE, return_attention)
     else:
         out, alpha, smax, sden, rstats = _apply(_SBFAttention, q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode,
-                                                         edge_row, heads, channels, return_attention)
+                                                         edge_row, heads, channels, return_attention, dropout)
     if rstats is not None:  # for a graph LayerNorm fused into the consumer (ops.row_chain(ln=...))
         out._x2g_rowstats = rstats
     if not return_attention:

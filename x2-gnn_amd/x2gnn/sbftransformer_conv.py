@@ -28,6 +28,12 @@ Extra keyword-only arguments for the in-framework fast path:
 table and triplets into line node e use row ``edge_row[e]``: X2-GNN's edge attribute is the
 embedding of the middle atom, identical for all triplets into e, xgnn.py:57-58) and
 ``edge_proj`` (``lin_edge(edge_attr)`` already computed, e.g. by the trunk's table chain).
+
+Attention dropout (``dropout`` > 0, training mode; reference sbftransformer_conv.py:153) multiplies the softmax
+weights by a counter-based keep mask inside the center kernels (include/x2g_staged.h): ``dropout_key`` is an
+int64 [2] device tensor (seed, step) the caller owns and does not change in place afterwards, ``dropout_salt``
+the layer's index.  Without a key the module makes one from ``torch.initial_seed()`` and its own call counter.
+The returned attention weights stay the softmax before dropout, like the reference's ``_alpha``.
 """
 from __future__ import annotations
 
@@ -48,6 +54,8 @@ class SBFTransformerConv(nn.Module):
         super().__init__()
         if not concat or (beta and root_weight):
             raise NotImplementedError("compiled configuration: concat=True, beta=False (X2-GNN's)")
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f"dropout probability has to be in [0, 1), but got {dropout}")
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
         self.sbf_dim, self.rbf_dim = sbf_dim, rbf_dim
         self.beta, self.root_weight, self.concat = False, root_weight, concat
@@ -63,13 +71,21 @@ class SBFTransformerConv(nn.Module):
         self.lin_sbf = Linear(sbf_dim, hc, bias=True)
         self.lin_rbf = Linear(rbf_dim, cin[0], bias=False)
         self._alpha = None
+        self._dropout_state = None  # int64 [2] on the device (seed, calls): the key when the caller gives none
+
+    def _own_dropout_key(self, device):
+        """(seed, call counter) advanced on the device, and a copy of it for this call's backward."""
+        st = self._dropout_state
+        if st is None or st.device != device:
+            seed = torch.initial_seed() & 0x7FFFFFFFFFFFFFFF
+            st = self._dropout_state = torch.tensor([seed, 0], dtype=torch.int64, device=device)
+        st[1] += 1
+        return st.clone()
 
     def forward(self, sbf, rbf, x, edge_index, edge_attr=None, return_attention_weights=None, *,
                 line_graph: Optional[ops.LineGraph] = None, edge_row=None, edge_proj=None,
-                assume_sorted: bool = False):
+                assume_sorted: bool = False, dropout_key=None, dropout_salt: int = 0):
         H, C = self.heads, self.out_channels
-        if self.training and self.dropout > 0:
-            raise NotImplementedError("attention dropout is not compiled (X2-GNN uses dropout=0)")
         if x.is_cuda and self.root_weight and x.dim() == 2:
             # one autograd node for the five projections: the backward chains the data
             # gradients into one buffer per input instead of autograd adds
@@ -105,8 +121,13 @@ class SBFTransformerConv(nn.Module):
         else:
             e, mode = None, ops.EDGE_NONE
         want = isinstance(return_attention_weights, bool)
+        dropout = None
+        if self.training and self.dropout > 0:
+            if dropout_key is None:
+                dropout_key = self._own_dropout_key(q.device)
+            dropout = (float(self.dropout), dropout_key, dropout_salt)
         res = ops.sbf_attention(q, k, v, skip, e, sbf, self.lin_sbf.weight, self.lin_sbf.bias, line_graph, H, C,
-                                edge_mode=mode, edge_row=edge_row, return_attention=want)
+                                edge_mode=mode, edge_row=edge_row, return_attention=want, dropout=dropout)
         if want:
             out, alpha = res
             if perm is not None:  # back to the caller's triplet order

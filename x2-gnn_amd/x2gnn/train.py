@@ -136,6 +136,8 @@ class Trainer:
     def capture(self, batch, warm=3):
         """Record forward+backward and the update as two HIP graphs (warm-up passes on a side
         stream first: forward+backward+exchange only, the parameters are not updated)."""
+        drop = self._dropout_state()
+        held = None if drop is None else drop.clone()  # (the warm-up passes draw masks: not steps of the run)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -143,6 +145,8 @@ class Trainer:
                 self.forward_backward(batch)
                 self.reduce()
         torch.cuda.current_stream().wait_stream(side)
+        if held is not None:
+            drop.copy_(held)
         # the forward+backward graph accumulates into a zeroed bucket and does not zero it itself:
         # the update graph's last kernel does (FlatAdam.step(zero_grads=True)), so a replayed step
         # has no fill launch; a caller replaying g_fb alone zeroes the bucket first
@@ -200,6 +204,13 @@ class Trainer:
         total = self.counts[1]
         return total if total is not None else batch.num_graphs * _world(self.group)
 
+    def _dropout_state(self):
+        """The trunk's attention-dropout (seed, step) buffer when the model trains with dropout, else None."""
+        trunk = getattr(self.model, "fin_model", self.model)
+        if getattr(trunk, "attn_dropout", 0.0) > 0:
+            return trunk.attn_dropout_state
+        return None
+
     def _names(self):
         """The optimizer's parameters by their names in the model, and the model's full state (detached
         aliases of the live tensors: parameters and buffers)."""
@@ -215,6 +226,8 @@ class Trainer:
             {"format": 1, "model": {name: tensor}, "ema": {name: tensor},
              "optimizer": {"exp_avg": {name: tensor}, "exp_avg_sq": {name: tensor}, "scalars": float32[16]}}
 
+        plus ``"attn_dropout_state"``: int64 [2] (seed, step) when the model has attention dropout, so a resumed
+        run draws the masks the uninterrupted one would.
         ``scalars`` carries the step count and the learning-rate schedule.  Every tensor is a clone
         (``torch.save`` takes the dict as it is).  "model" and "ema" have the model's own ``state_dict()`` keys
         — entries the optimizer does not average (buffers, frozen parameters) are the model's in both — so
@@ -230,9 +243,13 @@ class Trainer:
         ema = dict(model)
         if opt.ema is not None:
             ema.update(by_name(opt.ema))
-        return {"format": 1, "model": model, "ema": ema,
-                "optimizer": {"exp_avg": by_name(opt.exp_avg), "exp_avg_sq": by_name(opt.exp_avg_sq),
-                              "scalars": opt.scalars.clone()}}
+        sd = {"format": 1, "model": model, "ema": ema,
+              "optimizer": {"exp_avg": by_name(opt.exp_avg), "exp_avg_sq": by_name(opt.exp_avg_sq),
+                            "scalars": opt.scalars.clone()}}
+        drop = self._dropout_state()
+        if drop is not None:
+            sd["attn_dropout_state"] = drop.clone()
+        return sd
 
     def load_state_dict(self, sd):
         """Copy a ``state_dict()`` INTO the existing flat buffers (``copy_``; nothing is rebound, so graphs
@@ -264,7 +281,14 @@ class Trainer:
                                      f"expected {tuple(d.shape)}")
         if tuple(o["scalars"].shape) != tuple(opt.scalars.shape):
             raise ValueError(f"trainer state 'scalars' has shape {tuple(o['scalars'].shape)}")
+        drop = self._dropout_state()
+        if drop is not None and "attn_dropout_state" not in sd:
+            raise KeyError("trainer state: missing 'attn_dropout_state' (the model has attention dropout)")
+        if drop is not None and tuple(sd["attn_dropout_state"].shape) != (2,):
+            raise ValueError(f"trainer state 'attn_dropout_state' has shape {tuple(sd['attn_dropout_state'].shape)}")
         with torch.no_grad():
+            if drop is not None:
+                drop.copy_(sd["attn_dropout_state"])
             for part, dst in views.items():
                 if part == "ema" and opt.ema is None:
                     continue

@@ -106,17 +106,19 @@ class _XGNNBase(nn.Module):
 
 class xgnn_poly(_XGNNBase):
     def __init__(self, conv_layers=4, sbf_dim=7, rbf_dim=16, in_channels=256, heads=16, embedding_size=128,
-                 device="cpu"):
+                 device="cpu", attn_dropout=0.0, dropout_seed=0):
         super().__init__()
         trunk = SBFTransformer(conv_layers=conv_layers, emb_size=embedding_size, sbf_dim=sbf_dim, rbf_dim=rbf_dim,
-                               in_channels=in_channels, heads=heads)
+                               in_channels=in_channels, heads=heads, attn_dropout=attn_dropout,
+                               dropout_seed=dropout_seed)
         self._build(trunk, sbf_dim, rbf_dim, in_channels, embedding_size, device)
 
 
 class xgnn_poly_global(_XGNNBase):
     def __init__(self, conv_layers=4, sbf_dim=7, rbf_dim=16, in_channels=256, heads=16, embedding_size=128,
-                 device="cpu", pool_option="mean"):
+                 device="cpu", pool_option="mean", attn_dropout=0.0, dropout_seed=0):
         super().__init__()
         trunk = SBFTransformerGlobal(conv_layers=conv_layers, emb_size=embedding_size, sbf_dim=sbf_dim,
-                                     rbf_dim=rbf_dim, in_channels=in_channels, heads=heads, pool_option=pool_option)
+                                     rbf_dim=rbf_dim, in_channels=in_channels, heads=heads, pool_option=pool_option,
+                                     attn_dropout=attn_dropout, dropout_seed=dropout_seed)
         self._build(trunk, sbf_dim, rbf_dim, in_channels, embedding_size, device)
