@@ -240,6 +240,42 @@ class DeviceDataset:
         b._store["_x2g_count_z"] = self._assemble(idx, atoms_only=True)[0]["x"]
         return b, len(mine), int(idx.shape[0])
 
+    # ------------------------------------------------------------------------------------------ training order
+    def reordered(self, order):
+        """A new dataset holding the molecules ``order`` (indices into this one; any sequence, repeats and
+        subsets allowed), in that order: what ``DeviceDataset([mols[i] for i in order], device)`` builds, caches
+        included, made once from host prefix sums and one device ``index_select`` per tensor (no host copy of the
+        data and no recount of the triplets; while it runs both datasets' ``edge_attr`` are resident).
+
+        The reference permutes the dataset once and cuts its three splits from the permutation, unshuffled
+        (trainer.py:23-27), so every batch of every epoch is the same run of the permuted order:
+        ``ds.reordered(perm)`` stores the dataset in that order, every batch of ``loader(B, shuffle=False,
+        indices=split)`` is then a contiguous run of molecules, and its ``edge_attr`` rows one contiguous slab
+        ``edge_attr[edge_start[i]:edge_start[i + B]]`` of the dataset."""
+        idx = self._indices(order)
+        new = type(self).__new__(type(self))
+        new.device = self.device
+        new.nodes, new.edges = self.nodes[idx], self.edges[idx]
+        new.triplets, new.max_degree, new.symmetric = self.triplets[idx], self.max_degree[idx], self.symmetric[idx]
+        new.atom_start = np.concatenate([[0], np.cumsum(new.nodes)]).astype(np.int64)
+        new.edge_start = np.concatenate([[0], np.cumsum(new.edges)]).astype(np.int64)
+        new.num_features = self.num_features
+
+        def gather(start, new_start, counts):
+            # source row of every new row: the molecule's old start carried over its rows, plus the row's offset
+            g = np.repeat(start[idx] - new_start[:-1], counts) + np.arange(int(new_start[-1]), dtype=np.int64)
+            return torch.from_numpy(g).to(self.device)
+
+        atoms = gather(self.atom_start, new.atom_start, new.nodes)
+        rows = gather(self.edge_start, new.edge_start, new.edges)
+        mols = torch.from_numpy(idx).to(self.device)
+        new.x, new.atom_pos = self.x.index_select(0, atoms), self.atom_pos.index_select(0, atoms)
+        new.edge_index = self.edge_index.index_select(1, rows)
+        new.edge_attr = self.edge_attr.index_select(0, rows) if self.edge_attr is not None else None
+        new.y, new.mol_trips = self.y.index_select(0, mols), self.mol_trips.index_select(0, mols)
+        new._stage, new._slot, new._debug_fill = None, 0, None
+        return new
+
     # ------------------------------------------------------------------------------------------ fixed shape
     def capacity(self, index_lists, fillers=1) -> Capacity:
         """The one shape (:class:`x2gnn.padding.Capacity`) every batch of ``index_lists`` can be padded to by
