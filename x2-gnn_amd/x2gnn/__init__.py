@@ -8,14 +8,15 @@ Device side: ``libx2g.so`` (hand-written gfx950 HIP kernels behind the C ABI in
 from .data import Batch, Data, collate, molecule_to_data
 from .device_dataset import DeviceDataset
 from .layers import AtomWise, EmbeddingBlock, F_B_2D, MolWise, RadialBasis, ResidualLayer, poly_envelop
-from .model import LayerNorm, SBFTransformer, SBFTransformerGlobal
+from .model import LayerNorm, SBFTransformer, SBFTransformerGlobal, SBFTransformerMulti
 from .plan import GraphPlan
 from .sbftransformer_conv import SBFTransformerConv
 from .train import Evaluator, Inference, Trainer
-from .xgnn import xgnn_poly, xgnn_poly_global
+from .xgnn import xgnn_poly, xgnn_poly_global, xgnn_poly_multi
 
 __all__ = [
     "AtomWise", "Batch", "Data", "DeviceDataset", "EmbeddingBlock", "Evaluator", "F_B_2D", "GraphPlan", "Inference",
     "LayerNorm", "MolWise", "RadialBasis", "ResidualLayer", "SBFTransformer", "SBFTransformerConv",
-    "SBFTransformerGlobal", "Trainer", "collate", "molecule_to_data", "poly_envelop", "xgnn_poly", "xgnn_poly_global",
+    "SBFTransformerGlobal", "SBFTransformerMulti", "Trainer", "collate", "molecule_to_data", "poly_envelop",
+    "xgnn_poly", "xgnn_poly_global", "xgnn_poly_multi",
 ]

@@ -23,6 +23,8 @@ HEADER_PATH = os.environ.get("X2G_HEADER",
                              os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "x2g.h"))
 # the staged entry points' header, next to x2g.h: compiled into the same library, outside the recorded ABI
 STAGED_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_staged.h")
+# the multi-target entry points' header (the K-target readout heads, per-target metrics): a table of its own too
+MULTI_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_multi.h")
 
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int": ctypes.c_int,
             "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
@@ -108,22 +110,25 @@ def _read_header():
         return f.read()
 
 
-def _read_staged():
-    """(signatures, restypes) of x2g_staged.h, read like x2g.h; it declares functions only (no struct, no
-    constant: anything else raises).  Empty when the header is absent (an X2G_HEADER of an earlier tree)."""
-    if not os.path.exists(STAGED_HEADER_PATH):
+def _read_functions(path):
+    """(signatures, restypes) of a header next to x2g.h, read like it; it declares functions only (no struct,
+    no constant: anything else raises).  Empty when the header is absent (an X2G_HEADER of an earlier tree)."""
+    if not os.path.exists(path):
         return {}, {}
-    with open(STAGED_HEADER_PATH) as f:
+    with open(path) as f:
         sig, res, structs, consts = parse_header(f.read())
     if structs or consts:
-        raise ValueError(f"x2g_staged.h declares more than functions: {sorted(structs) + sorted(consts)}")
+        raise ValueError(f"{os.path.basename(path)} declares more than functions: "
+                         f"{sorted(structs) + sorted(consts)}")
     return sig, res
 
 
 # name -> argtypes / restype of every function, name -> Structure of every typedef struct, and the #defines
 SIGNATURES, RESTYPES, STRUCTS, CONSTS = parse_header(_read_header())
 # the same for the staged entry points (x2g_staged.h), kept apart: SIGNATURES stays exactly x2g.h's
-STAGED_SIGNATURES, STAGED_RESTYPES = _read_staged()
+STAGED_SIGNATURES, STAGED_RESTYPES = _read_functions(STAGED_HEADER_PATH)
+# and for the multi-target entry points (x2g_multi.h)
+MULTI_SIGNATURES, MULTI_RESTYPES = _read_functions(MULTI_HEADER_PATH)
 
 _lib = None
 
@@ -139,12 +144,13 @@ def load():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = RESTYPES[name]
-        for name, args in STAGED_SIGNATURES.items():
-            # (a library built from an earlier tree, X2G_LIB, has none of them: calling one then raises)
-            fn = getattr(lib, name, None)
-            if fn is not None:
-                fn.argtypes = args
-                fn.restype = STAGED_RESTYPES[name]
+        for sigs, res in ((STAGED_SIGNATURES, STAGED_RESTYPES), (MULTI_SIGNATURES, MULTI_RESTYPES)):
+            for name, args in sigs.items():
+                # (a library built from an earlier tree, X2G_LIB, has none of them: calling one then raises)
+                fn = getattr(lib, name, None)
+                if fn is not None:
+                    fn.argtypes = args
+                    fn.restype = res[name]
         _lib = lib
     return _lib
 

@@ -314,15 +314,28 @@ def _is_symmetric(ei, n):
     return bool(np.array_equal(sf, np.sort(rev)))
 
 
+def molecule_targets(mols):
+    """``y`` of molecule dicts as float32: [B] where every molecule carries one value (a scalar, or absent: 0),
+    [B, K] where each carries the same K > 1 values (a K-target model's labels)."""
+    ys = [np.asarray(m.get("y", 0.0), dtype=np.float32).reshape(-1) for m in mols]
+    K = ys[0].shape[0] if ys else 1
+    if any(y.shape[0] != K for y in ys) or K < 1:
+        raise ValueError(f"every molecule needs the same number of targets, got {sorted({y.shape[0] for y in ys})}")
+    y = np.stack(ys) if ys else np.zeros((0, 1), np.float32)
+    return y.reshape(-1) if K == 1 else y
+
+
 def molecule_to_data(mol: dict) -> Data:
-    """One synthetic/xyz molecule dict (see :mod:`x2gnn.synth`) as a ``Data``."""
+    """One synthetic/xyz molecule dict (see :mod:`x2gnn.synth`) as a ``Data`` (K > 1 targets: ``y`` [1, K], as
+    PyG stores them, so that a batch's is [B, K])."""
+    y = molecule_targets([mol])
     d = Data(
         x=torch.as_tensor(mol["x"], dtype=torch.int64),
         atom_pos=torch.as_tensor(mol["atom_pos"], dtype=torch.float32),
         edge_index=torch.as_tensor(mol["edge_index"], dtype=torch.int64),
         edge_attr=torch.as_tensor(mol["edge_attr"], dtype=torch.float32) if "edge_attr" in mol else None,
         edge_num=int(mol["edge_num"]),
-        y=float(mol.get("y", 0.0)),
+        y=float(y[0]) if y.ndim == 1 else torch.from_numpy(y),
     )
     object.__setattr__(d, "_meta", {"nodes": np.array([len(mol["x"])]),
                                     "edges": np.array([int(mol["edge_num"])]),
@@ -351,7 +364,7 @@ def collate(mols) -> Batch:
         st["edge_attr"] = torch.from_numpy(np.concatenate([np.asarray(m["edge_attr"], dtype=np.float32)
                                                            for m in mols]))
     st["edge_num"] = torch.from_numpy(edges.copy())
-    st["y"] = torch.from_numpy(np.array([float(m.get("y", 0.0)) for m in mols], dtype=np.float32))
+    st["y"] = torch.from_numpy(molecule_targets(mols))  # [B], or [B, K] for K-wide labels
     # np.repeat: torch.repeat_interleave took 0.2-7 ms of a 128-molecule collate, after the edge_attr copy
     st["batch"] = torch.from_numpy(np.repeat(np.arange(B, dtype=np.int64), nodes))
     st["ptr"] = torch.from_numpy(np.concatenate([[0], np.cumsum(nodes)]))

@@ -318,6 +318,41 @@ def prepare_target(dataset: CollatedDataset, target: int, atom_ref: torch.Tensor
     return calib
 
 
+def prepare_targets(dataset: CollatedDataset, targets, standardize: bool = True,
+                    atom_ref: torch.Tensor | None = None) -> list:
+    """``prepare_target`` for several targets at once, for a K-target model: ``dataset.data.y`` ([M, 12]) becomes
+    [M, len(targets)] in place, column k holding what ``prepare_target(dataset, targets[k])`` gives (the
+    atom-reference subtraction and the eV conversion of train_ema.py:29-38, the same arithmetic) and, with
+    ``standardize``, divided by that column's standard deviation over the dataset (population, formed in fp64:
+    twelve properties of very different scale under one unweighted loss).  Returns per target the scale that
+    turns a standardised MAE back into the reference's printed units: standard deviation x ``print_calibration``
+    (the calibration alone without ``standardize``)."""
+    ref = atom_reference_table() if atom_ref is None else atom_ref
+    counts = dataset.atoms_per_molecule()
+    owner = torch.arange(len(dataset)).repeat_interleave(counts)
+    y_all = dataset.data.y
+    cols, scales = [], []
+    for target in targets:
+        mol_ref = torch.zeros(len(dataset), dtype=ref.dtype).index_add_(0, owner, ref[target][dataset.data.x])
+        y = y_all[:, target].squeeze() - mol_ref
+        calib = 1
+        if target in EV_TARGETS:
+            y = y * HARTREE_TO_EV
+            calib = PRINT_CALIBRATION_EV
+        if standardize:
+            y64 = y.to(torch.float64)
+            std = float((y64 - y64.mean()).pow(2).mean().sqrt())
+            if not std > 0:
+                raise ValueError(f"target {target} is constant over the dataset: it cannot be standardised")
+            y = (y64 / std).to(y.dtype)
+            scales.append(std * calib)
+        else:
+            scales.append(float(calib))
+        cols.append(y)
+    dataset.data.y = torch.stack(cols, dim=1)
+    return scales
+
+
 def model_for_target(target: int, cfg: dict, device="cuda", pool_option="mean"):
     """train_ema.py:41-44: AtomWise ``xgnn_poly`` for targets 6-11, MolWise ``xgnn_poly_global``
     (``pool_option`` 'mean' or 'add') for 0-5."""

@@ -16,7 +16,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .data import Batch
+from .data import Batch, molecule_targets
 from .padding import Capacity, solve_capacity
 
 _RING = 4  # pinned staging slots for the offset block: a slot is rewritten only after its copy has finished
@@ -64,10 +64,12 @@ class DeviceDataset:
     Host caches (numpy, one entry per molecule): ``nodes``, ``edges``, ``triplets``, ``max_degree``,
     ``symmetric`` and the prefix sums ``atom_start`` / ``edge_start`` ([M + 1]).  Device tensors: ``x`` int64
     [N_all], ``atom_pos`` f32 [N_all, 3], ``edge_index`` int64 [2, E_all] (molecule-local), ``edge_attr`` f32
-    [E_all, F] or None, ``y`` f32 [M], ``mol_trips`` int64 [M]."""
+    [E_all, F] or None, ``y`` f32 [M] (K > 1 targets per molecule: [M, K], gathered per batch by one
+    ``index_select`` on the uploaded molecule ids instead of by the assemble kernel), ``mol_trips`` int64 [M]."""
 
     def __init__(self, mols, device):
-        """``mols``: molecule dicts as :func:`x2gnn.data.collate` takes them."""
+        """``mols``: molecule dicts as :func:`x2gnn.data.collate` takes them (``y``: one value each, or the same
+        K values each)."""
         M = len(mols)
         nodes = np.fromiter((len(m["x"]) for m in mols), dtype=np.int64, count=M)
         edges = np.fromiter((int(m["edge_num"]) for m in mols), dtype=np.int64, count=M)
@@ -81,17 +83,22 @@ class DeviceDataset:
               if M else np.zeros((2, 0), np.int64))
         attr = (np.concatenate([np.asarray(m["edge_attr"], dtype=np.float32) for m in mols])
                 if M and "edge_attr" in mols[0] else None)
-        y = np.array([float(m.get("y", 0.0)) for m in mols], dtype=np.float32)
+        y = molecule_targets(mols)
         self._init(nodes, edges, x, pos, ei, attr, y, device)
 
     @classmethod
-    def from_collated(cls, dataset, device):
+    def from_collated(cls, dataset, device, num_target=1):
         """From a :class:`x2gnn.datasets.CollatedDataset` (a PyG ``InMemoryDataset`` processed file) after
-        ``prepare_target``, so that ``y`` is one value per molecule."""
+        ``prepare_target``, so that ``y`` is one value per molecule; with ``num_target`` = K > 1 after
+        ``prepare_targets``, ``y`` [M, K]."""
         st, sl = dataset.data._store, dataset.slices
         M = len(dataset)
         y = st["y"]
-        if y.dim() != 1 or int(y.shape[0]) != M:
+        if int(num_target) > 1:
+            if y.dim() != 2 or tuple(y.shape) != (M, int(num_target)):
+                raise ValueError(f"y must be [M, K] = [{M}, {int(num_target)}] (run datasets.prepare_targets first), "
+                                 f"got {tuple(y.shape)}")
+        elif y.dim() != 1 or int(y.shape[0]) != M:
             raise ValueError(f"y must be [M] = [{M}] (run datasets.prepare_target first), got {tuple(y.shape)}")
         nodes = np.diff(sl["x"].numpy().astype(np.int64))
         edges = np.diff(sl["edge_index"].numpy().astype(np.int64))
@@ -194,11 +201,14 @@ class DeviceDataset:
         src, dst, src_t, dst_t, atom_t, mol_ptr, line_ptr = torch.split(i32, [E, E, E, E, N, B + 1, B + 1])
         pos, y = torch.split(f32, [3 * N, B])
         off = self._upload(block)
+        wide = self.y.dim() == 2  # K targets per molecule: the kernel gathers no y (both pointers NULL)
         call("x2g_batch_assemble", ptr(self.x), ptr(self.atom_pos), ptr(self.edge_index),
-             int(self.edge_index.shape[1]), ptr(self.edge_attr) if F else None, F, ptr(self.y), ptr(self.mol_trips),
-             ptr(off), B, N, E, ptr(x), ptr(pos), ptr(batch), ptr(p), ptr(ei), ptr(attr), ptr(edge_num), ptr(y),
-             ptr(src), ptr(dst), ptr(src_t), ptr(dst_t), ptr(atom_t), ptr(mol_ptr), ptr(line_ptr), ptr(trips),
-             stream_ptr(dev))
+             int(self.edge_index.shape[1]), ptr(self.edge_attr) if F else None, F, None if wide else ptr(self.y),
+             ptr(self.mol_trips), ptr(off), B, N, E, ptr(x), ptr(pos), ptr(batch), ptr(p), ptr(ei), ptr(attr),
+             ptr(edge_num), None if wide else ptr(y), ptr(src), ptr(dst), ptr(src_t), ptr(dst_t), ptr(atom_t),
+             ptr(mol_ptr), ptr(line_ptr), ptr(trips), stream_ptr(dev))
+        if wide:  # the molecule ids are the offset block's third run
+            y = self.y.index_select(0, off[2 * B:3 * B])
         out = {"x": x, "atom_pos": pos.view(N, 3), "edge_index": ei.view(2, E), "edge_attr": attr,
                "edge_num": edge_num, "y": y, "batch": batch, "ptr": p, "_x2g_edge_src": src, "_x2g_edge_dst": dst,
                "_x2g_mol_ptr": mol_ptr, "_x2g_line_ptr": line_ptr, "_x2g_dst_type": dst_t, "_x2g_src_type": src_t,

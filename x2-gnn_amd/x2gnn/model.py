@@ -49,6 +49,47 @@ def _plan_of(data, edge_index_0, atom_batch):
     return plan if plan is not None else GraphPlan.from_line_data(data, edge_index_0, atom_batch)
 
 
+class _ReadoutFamily:
+    """One family of readouts (one per layer output) during a trunk forward: collects the layer outputs, then
+    runs the family's batched pool and its batched readout MLPs, or readout by readout where those do not apply."""
+
+    def __init__(self, readouts, readout_fn, feature_fn=None, pool_fn=None, pool_out=None):
+        self.readouts, self.readout_fn, self.feature_fn = readouts, readout_fn, feature_fn
+        self.pool_fn, self.pool_out = pool_fn, pool_out
+
+    def start(self, is_cuda):
+        self.results, self.feats = None, []
+        self.grouped = is_cuda and self.feature_fn is not None
+        self.pooled_xs = [] if self.grouped and self.pool_fn is not None else None
+
+    def add(self, i, x):
+        if self.pooled_xs is not None:
+            self.pooled_xs.append(x)
+        elif self.grouped:
+            self.feats.append(self.feature_fn(i, x))
+        else:
+            r = self.readout_fn(i, x)
+            self.results = r if self.results is None else self.results + r
+
+    def finish(self):
+        feats, results = self.feats, self.results
+        if self.pooled_xs is not None:
+            feats = self.pool_fn(self.pooled_xs)
+            if feats is None:
+                feats = [self.feature_fn(i, x) for i, x in enumerate(self.pooled_xs)]
+        if self.grouped:
+            mlps = [r.mlp for r in self.readouts]
+            if ops.readout_mlps_supported(feats, mlps):
+                r = ops.readout_mlps(feats, mlps, pool=self.pool_out)
+                if self.pool_out is not None:
+                    r._x2g_pooled = True
+                return r
+            for m, f in zip(mlps, feats):
+                r = run_mlp(m, f)
+                results = r if results is None else results + r
+        return results
+
+
 class _Trunk(nn.Module):
     def _build(self, conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads, readout, attn_dropout=0.0,
                dropout_seed=0):
@@ -93,9 +134,11 @@ class _Trunk(nn.Module):
         return ([(mods[0], ops.ACT_SILU, -1), (mods[2], ops.ACT_NONE, 0)]
                 + [(c.lin_edge, ops.ACT_NONE, 1) for c in self.convs])
 
-    def _layers(self, data, plan, readout_fn, feature_fn=None, pool_fn=None, pool_out=None):
-        """The conv layers with their readouts; ``pool_out = (seg_rowptr, S)``: the batched readout heads
-        may sum the per-atom results per molecule themselves (the result then carries ``_x2g_pooled``)."""
+    def _layers(self, data, plan, families):
+        """The conv layers with their readouts: ``families``, the _ReadoutFamily list of this forward (one for the
+        single-family trunks, two for SBFTransformerMulti); returns their results in that order.  A family with
+        ``pool_out = (seg_rowptr, S)``: the batched readout heads may sum the per-atom results per molecule
+        themselves (the result then carries ``_x2g_pooled``)."""
         per_dst = "edge_attr_row" in data._store
         edge_proj = data._store.get("_x2g_edge_proj") if per_dst else None
         # lin_edge tables precomputed by the featurisation's table chain, or edgenn here
@@ -106,25 +149,16 @@ class _Trunk(nn.Module):
         # layer order (deterministic).  (Run on a second stream, overlapping the next layer, they
         # measured slower: 6.30 vs 6.00 ms/step — the persistent one-workgroup-per-CU kernels of the
         # main chain lose more to the shared CUs than the overlap gains; that path is gone.)
-        results = None
-        # Batched readout MLPs: collect every readout's MLP input, then one batched launch per MLP
-        # layer for all readouts (ops.readout_mlps) instead of three launches per readout.
-        grouped = out.is_cuda and feature_fn is not None
-        feats = []
-        # the readouts' edge -> atom pools of every layer output as one launch each way (pool_fn,
-        # ops.rbf_pool_batch) after the last layer; per readout where that is unsupported
-        pooled_xs = [] if grouped and pool_fn is not None else None
+        # Batched readout MLPs: each family collects every readout's MLP input, then one batched launch per
+        # MLP layer for all its readouts (ops.readout_mlps) instead of three launches per readout; the
+        # readouts' edge -> atom pools of every layer output as one launch each way (pool_fn,
+        # ops.rbf_pool_batch) after the last layer; per readout where that is unsupported (_ReadoutFamily)
+        for f in families:
+            f.start(out.is_cuda)
 
         def readout(i, x):
-            nonlocal results
-            if pooled_xs is not None:
-                pooled_xs.append(x)
-                return
-            if grouped:
-                feats.append(feature_fn(i, x))
-                return
-            r = readout_fn(i, x)
-            results = r if results is None else results + r
+            for f in families:
+                f.add(i, x)
 
         # gradient fan-in in place: the layer inputs and the radial basis feed several fused ops each
         fan = self._fan_in_ok(data, out)
@@ -153,27 +187,12 @@ class _Trunk(nn.Module):
             if fan:
                 out._x2g_fanin = ops.FanIn()
             readout(i + 1, out)
-        if pooled_xs is not None:
-            feats = pool_fn(pooled_xs)
-            if feats is None:
-                feats = [feature_fn(i, x) for i, x in enumerate(pooled_xs)]
-        if grouped:
-            mlps = [r.mlp for r in self.readouts]
-            if ops.readout_mlps_supported(feats, mlps):
-                r = ops.readout_mlps(feats, mlps, pool=pool_out)
-                if pool_out is not None:
-                    r._x2g_pooled = True
-                return r
-            for m, f in zip(mlps, feats):
-                r = run_mlp(m, f)
-                results = r if results is None else results + r
-        return results
+        return [f.finish() for f in families]
 
-
-    def _pool_batch(self, xs, rbf, edge_index_0, plan):
+    def _pool_batch(self, xs, rbf, edge_index_0, plan, readouts=None):
         """Every readout's edge -> atom pool (readout.py:39-41 / 66-67) in one launch each way, or
         None where the batched kernels do not cover the shapes."""
-        lins = [r.lin_rbf for r in self.readouts]
+        lins = [r.lin_rbf for r in (self.readouts if readouts is None else readouts)]
         if rbf is None or len(xs) != len(lins) or not ops.rbf_pool_batch_supported(xs, rbf, [l.weight for l in lins]):
             return None
         return ops.rbf_pool_batch(xs, rbf, [l.weight for l in lins], [l.bias for l in lins], edge_index_0,
@@ -221,19 +240,17 @@ class _Trunk(nn.Module):
         return self.af_skip[i](out)
 
 
-class SBFTransformer(_Trunk):
-    """Trunk with per-atom readouts (extensive targets, reference model.py:11-54)."""
+def _check_targets(n, least=1):
+    n = int(n)
+    if not least <= n <= ops.HEADS_K_MAX_TARGETS:
+        raise ValueError(f"{least} .. {ops.HEADS_K_MAX_TARGETS} targets per readout family, got {n}")
+    return n
 
-    def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8, attn_dropout=0.0,
-                 dropout_seed=0):
-        super().__init__()
-        self._build(conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads,
-                    lambda: AtomWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=1),
-                    attn_dropout=attn_dropout, dropout_seed=dropout_seed)
 
-    def forward(self, data, edge_index_0, atom_batch):
-        plan = _plan_of(data, edge_index_0, atom_batch)
+class _AtomReadouts:
+    """The per-atom family of a trunk: AtomWise ``self.readouts``, summed per molecule (model.py:11-54)."""
 
+    def _atom_family(self, data, edge_index_0, plan):
         def readout(i, x):
             return self.readouts[i](x=x, rbf=data.node_rbf, num_atoms=plan.num_atoms, edge_index_0=edge_index_0,
                                     atom_rowptr=plan.atom_rowptr)
@@ -243,42 +260,113 @@ class SBFTransformer(_Trunk):
                                              edge_index_0=edge_index_0, atom_rowptr=plan.atom_rowptr)
 
         def pools(xs):
-            return self._pool_batch(xs, data.node_rbf, edge_index_0, plan)
+            return self._pool_batch(xs, data.node_rbf, edge_index_0, plan, self.readouts)
 
         # the global add pool (model.py:53) fused into the batched readout heads where they run
         pool_out = (plan.mol_ptr, plan.out_graphs) if plan.out_graphs == plan.num_graphs else None
-        per_atom = self._layers(data, plan, readout, features, pools, pool_out=pool_out)
+        return _ReadoutFamily(self.readouts, readout, features, pools, pool_out)
+
+    @staticmethod
+    def _atom_pooled(per_atom, plan):
+        """[B, K]: the family's result summed per molecule (by the fused heads already, or here)."""
         if getattr(per_atom, "_x2g_pooled", False):
-            return per_atom.view(-1)
-        return ops.segment_sum(per_atom, plan.mol_ptr, plan.out_graphs).view(-1)
+            return per_atom
+        return ops.segment_sum(per_atom, plan.mol_ptr, plan.out_graphs)
 
 
-class SBFTransformerGlobal(_Trunk):
-    """Trunk with per-molecule readouts (intensive targets, reference model.py:56-98)."""
+class _MolReadouts:
+    """The per-molecule family of a trunk: MolWise readouts (model.py:56-98)."""
 
-    def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8, pool_option="mean",
-                 attn_dropout=0.0, dropout_seed=0):
-        super().__init__()
-        self._build(conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads,
-                    lambda: MolWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=1, pool_option=pool_option),
-                    attn_dropout=attn_dropout, dropout_seed=dropout_seed)
-
-    def forward(self, data, edge_index_0, atom_batch):
-        plan = _plan_of(data, edge_index_0, atom_batch)
-
+    def _mol_family(self, data, edge_index_0, atom_batch, plan, readouts):
         kw = dict(rbf=data.node_rbf, num_atoms=plan.num_atoms, edge_index_0=edge_index_0, atom_batch=atom_batch,
                   dim_size=plan.out_graphs, atom_rowptr=plan.atom_rowptr, mol_rowptr=plan.mol_ptr[: plan.out_graphs + 1])
 
         def readout(i, x):
-            return self.readouts[i](x=x, **kw)
+            return readouts[i](x=x, **kw)
 
         def features(i, x):
-            return self.readouts[i].features(x=x, **kw)
+            return readouts[i].features(x=x, **kw)
 
         def pools(xs):
-            atoms = self._pool_batch(xs, data.node_rbf, edge_index_0, plan)
+            atoms = self._pool_batch(xs, data.node_rbf, edge_index_0, plan, readouts)
             if atoms is None:
                 return None
-            return [r.finish(a, atom_batch, plan.out_graphs, kw["mol_rowptr"]) for r, a in zip(self.readouts, atoms)]
+            return [r.finish(a, atom_batch, plan.out_graphs, kw["mol_rowptr"]) for r, a in zip(readouts, atoms)]
 
-        return self._layers(data, plan, readout, features, pools).view(-1)
+        return _ReadoutFamily(readouts, readout, features, pools)
+
+
+class SBFTransformer(_Trunk, _AtomReadouts):
+    """Trunk with per-atom readouts (extensive targets, reference model.py:11-54).  ``num_target`` = K: the
+    readouts end in Linear(D, K) and ``forward`` returns [B, K] (K = 1: [B], the reference's tensor)."""
+
+    def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8, attn_dropout=0.0,
+                 dropout_seed=0, num_target=1):
+        super().__init__()
+        self.num_target = num_target = _check_targets(num_target)
+        self._build(conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads,
+                    lambda: AtomWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=num_target),
+                    attn_dropout=attn_dropout, dropout_seed=dropout_seed)
+
+    def forward(self, data, edge_index_0, atom_batch):
+        plan = _plan_of(data, edge_index_0, atom_batch)
+        (per_atom,) = self._layers(data, plan, [self._atom_family(data, edge_index_0, plan)])
+        out = self._atom_pooled(per_atom, plan)
+        return out.view(-1) if self.num_target == 1 else out
+
+
+class SBFTransformerGlobal(_Trunk, _MolReadouts):
+    """Trunk with per-molecule readouts (intensive targets, reference model.py:56-98); ``num_target`` as
+    SBFTransformer's."""
+
+    def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8, pool_option="mean",
+                 attn_dropout=0.0, dropout_seed=0, num_target=1):
+        super().__init__()
+        self.num_target = num_target = _check_targets(num_target)
+        self._build(conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads,
+                    lambda: MolWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=num_target,
+                                    pool_option=pool_option),
+                    attn_dropout=attn_dropout, dropout_seed=dropout_seed)
+
+    def forward(self, data, edge_index_0, atom_batch):
+        plan = _plan_of(data, edge_index_0, atom_batch)
+        (out,) = self._layers(data, plan, [self._mol_family(data, edge_index_0, atom_batch, plan, self.readouts)])
+        return out.view(-1) if self.num_target == 1 else out
+
+
+class SBFTransformerMulti(_Trunk, _AtomReadouts, _MolReadouts):
+    """One trunk, two readout families (the multi-head readout of all 12 QM9 properties): ``readouts``, AtomWise
+    with ``atom_targets`` outputs summed per molecule (extensive targets), and ``mol_readouts``, MolWise with
+    ``mol_targets`` outputs (intensive targets).  ``forward`` returns [B, mol_targets + atom_targets], the
+    per-molecule columns first (QM9's order: targets 0-5 intensive, 6-11 extensive).  Either count may be 0; that
+    family then has no modules, and the model is SBFTransformer / SBFTransformerGlobal with a 2-d result."""
+
+    def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8, atom_targets=6,
+                 mol_targets=6, pool_option="mean", attn_dropout=0.0, dropout_seed=0):
+        super().__init__()
+        self.atom_targets, self.mol_targets = _check_targets(atom_targets, 0), _check_targets(mol_targets, 0)
+        self.num_target = self.atom_targets + self.mol_targets
+        if self.num_target < 1:
+            raise ValueError("atom_targets + mol_targets must be at least 1")
+        self._build(conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads,
+                    lambda: AtomWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=max(self.atom_targets, 1)),
+                    attn_dropout=attn_dropout, dropout_seed=dropout_seed)
+        if not self.atom_targets:
+            self.readouts = ModuleList()
+        self.mol_readouts = ModuleList([MolWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=self.mol_targets,
+                                                pool_option=pool_option)
+                                        for _ in range(conv_layers + 1 if self.mol_targets else 0)])
+
+    def forward(self, data, edge_index_0, atom_batch):
+        plan = _plan_of(data, edge_index_0, atom_batch)
+        families = []
+        if self.atom_targets:
+            families.append(self._atom_family(data, edge_index_0, plan))
+        if self.mol_targets:
+            families.append(self._mol_family(data, edge_index_0, atom_batch, plan, self.mol_readouts))
+        res = self._layers(data, plan, families)
+        if self.atom_targets:
+            res[0] = self._atom_pooled(res[0], plan)
+        if len(res) == 1:
+            return res[0]
+        return torch.cat([res[1], res[0]], dim=1)

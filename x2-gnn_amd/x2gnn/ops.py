@@ -810,9 +810,7 @@ class _ReadoutMLPs(torch.autograd.Function):
             jobs = (ChainFwdJob * G)(*[ChainFwdJob(_dp(xs[g]), None, ctypes.addressof(stages[g]),
                                                    in_t[g].data_ptr() if grad else None) for g in range(G)])
             call("x2g_chain_fwd_batch", jobs, G, 2, R, D, st)
-            heads = (HeadGroup * G)(*[HeadGroup(_dp(h2[g]), _dp(W3[g]), _dp(B3[g]), None, None, None)
-                                      for g in range(G)])
-            out = _head_fwd(heads, G, R, D, pool, f32, st)
+            out = _heads_fwd(h2, W3, B3, G, R, D, pool, f32, st)
             if grad:
                 ctx.save_for_backward(*h2, *z1, *z2, WT, in_t, *(xs if ctx.rm0 else ()))
             ctx.G, ctx.params = G, params
@@ -822,8 +820,7 @@ class _ReadoutMLPs(torch.autograd.Function):
             grp = (DenseFwdGroup * G)(*[DenseFwdGroup(_dp(src[g]), _dp(w[g]), _dp(b[g]), None, _dp(y[g]), _dp(z[g]))
                                         for g in range(G)])
             call("x2g_dense_fwd_batched", grp, G, R, D, D, ACT_SILU, st)
-        heads = (HeadGroup * G)(*[HeadGroup(_dp(h2[g]), _dp(W3[g]), _dp(B3[g]), None, None, None) for g in range(G)])
-        out = _head_fwd(heads, G, R, D, pool, f32, st)
+        out = _heads_fwd(h2, W3, B3, G, R, D, pool, f32, st)
         ctx.save_for_backward(*xs, *h1, *z1, *h2, *z2)
         ctx.G, ctx.params = G, params
         return out
@@ -843,25 +840,37 @@ class _ReadoutMLPs(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         lib = _lib.load()
         st = stream_ptr()
+        K = W3[0].shape[0]
         dout = _f32(dout.reshape(-1))
         # head: dh2_g = dout w3_g; dW3_g, db3_g
         dh2 = [torch.empty(R, D, **f32) for _ in range(G)]
         dest3 = _WGradDest(list(W3) + list(B3), dev)
         dw3, db3 = dest3.bufs[:G], dest3.bufs[G:]
         g3 = dest3.grads()
-        heads = (HeadGroup * G)(*[HeadGroup(_dp(h2[g]), _dp(W3[g]), None, _dp(dh2[g]), _dp(dw3[g]), _dp(db3[g]))
-                                  for g in range(G)])
-        ws_bytes = int(lib.x2g_readout_head_bwd_workspace(R, D, G))
-        hflags, ws = dest3.flags(R), dest3.workspace(ws_bytes)
-        if ctx.pool is not None:  # dout per molecule, broadcast to its rows inside the head kernel
-            seg_rowptr, n_seg = ctx.pool
-            call("x2g_readout_head_pool_bwd", ptr(dout), ptr(seg_rowptr), n_seg, heads, G, R, D, hflags, ptr(ws),
-                 ws_bytes, st)
+        if K > 1:  # the K-target heads (x2g_multi.h): dout [R or n_seg, K]
+            seg_rowptr, n_seg = ctx.pool if ctx.pool is not None else (None, 0)
+            ws_bytes = int(lib.x2g_readout_heads_k_bwd_workspace(R, D, K, G))
+            hflags, ws = dest3.flags(R), dest3.workspace(ws_bytes)
+            call("x2g_readout_heads_k_bwd", ptr(dout), ptr(seg_rowptr), n_seg, _ptrs(h2), _ptrs(W3), _ptrs(dh2),
+                 _ptrs(dw3), _ptrs(db3), G, R, D, K, hflags, ptr(ws), ws_bytes, st)
+            if dest3.deferral:  # readout g's slabs: splits x (K*D weights, then K biases) floats
+                splits = int(lib.x2g_readout_heads_k_bwd_splits(R))
+                dest3.queue(*[(g * splits * (K * D + K) * 4, splits, K * D, K, dw3[g], db3[g]) for g in range(G)])
+            heads = None
         else:
-            call("x2g_readout_head_bwd", ptr(dout), heads, G, R, D, hflags, ptr(ws), ws_bytes, st)
-        if dest3.deferral:  # readout g's slabs: splits x (D weights + 1 bias) floats, one readout after another
-            splits = int(lib.x2g_readout_head_bwd_splits(R))
-            dest3.queue(*[(g * splits * (D + 1) * 4, splits, D, 1, dw3[g], db3[g]) for g in range(G)])
+            heads = (HeadGroup * G)(*[HeadGroup(_dp(h2[g]), _dp(W3[g]), None, _dp(dh2[g]), _dp(dw3[g]), _dp(db3[g]))
+                                      for g in range(G)])
+            ws_bytes = int(lib.x2g_readout_head_bwd_workspace(R, D, G))
+            hflags, ws = dest3.flags(R), dest3.workspace(ws_bytes)
+            if ctx.pool is not None:  # dout per molecule, broadcast to its rows inside the head kernel
+                seg_rowptr, n_seg = ctx.pool
+                call("x2g_readout_head_pool_bwd", ptr(dout), ptr(seg_rowptr), n_seg, heads, G, R, D, hflags, ptr(ws),
+                     ws_bytes, st)
+            else:
+                call("x2g_readout_head_bwd", ptr(dout), heads, G, R, D, hflags, ptr(ws), ws_bytes, st)
+            if dest3.deferral:  # readout g's slabs: splits x (D weights + 1 bias) floats, one readout after another
+                splits = int(lib.x2g_readout_head_bwd_splits(R))
+                dest3.queue(*[(g * splits * (D + 1) * 4, splits, D, 1, dw3[g], db3[g]) for g in range(G)])
         if ctx.chain:  # both hidden layers' data gradients in one launch; dW / db from the T layout
             dfeat = [torch.empty(R, D, **f32) for _ in range(G)]
             dz_t = torch.empty_like(in_t)
@@ -901,6 +910,24 @@ class _ReadoutMLPs(torch.autograd.Function):
         return (None, None, *dfeat, *pg)
 
 
+def _ptrs(ts):
+    """A host array of the tensors' device pointers (None -> NULL), as x2g_multi.h's entries take them."""
+    return (ctypes.c_void_p * len(ts))(*[_dp(t) for t in ts])
+
+
+def _heads_fwd(h2, W3, B3, G, R, D, pool, f32, st):
+    """The readouts' last layers summed over readouts: Linear(D, 1) through x2g_readout_head_(pool_)fwd, a
+    Linear(D, K) with K > 1 through x2g_readout_heads_k_fwd -> [R or n_seg, K]."""
+    K = W3[0].shape[0]
+    if K == 1:
+        heads = (HeadGroup * G)(*[HeadGroup(_dp(h2[g]), _dp(W3[g]), _dp(B3[g]), None, None, None) for g in range(G)])
+        return _head_fwd(heads, G, R, D, pool, f32, st)
+    seg_rowptr, n_seg = pool if pool is not None else (None, 0)
+    out = torch.empty(R if pool is None else n_seg, K, **f32)
+    call("x2g_readout_heads_k_fwd", _ptrs(h2), _ptrs(W3), _ptrs(B3), G, R, D, K, ptr(seg_rowptr), n_seg, ptr(out), st)
+    return out
+
+
 def _head_fwd(heads, G, R, D, pool, f32, st):
     """sum_g head_g(h_g) -> [R, 1] per row, or [n_seg, 1] summed per segment of rows with the pool
     (x2g_readout_head_pool_fwd: the global add pool fused)."""
@@ -933,7 +960,8 @@ def _readout_chain_ok(R, D, G, *weights):
 
 def readout_mlps_supported(feats, mlps):
     """True when _ReadoutMLPs covers these readouts (same row count and width, the 3-layer
-    Linear/SiLU/Linear/SiLU/Linear(D,1) MLP with biases, G <= 8, compiled widths)."""
+    Linear/SiLU/Linear/SiLU/Linear(D,K) MLP with biases, the same K <= 16 targets in every readout, G <= 8,
+    compiled widths)."""
     from .layers import Linear as _Lin
     G = len(feats)
     if G < 1 or G > 8 or not all(f.is_cuda and f.dim() == 2 and f.shape == feats[0].shape for f in feats):
@@ -951,14 +979,20 @@ def readout_mlps_supported(feats, mlps):
             return False
         if tuple(mods[0].weight.shape) != (D, D) or tuple(mods[2].weight.shape) != (D, D):
             return False
-        if tuple(mods[4].weight.shape) != (1, D):
+        K = mods[4].weight.shape[0]
+        if tuple(mods[4].weight.shape) != (K, D) or not 1 <= K <= HEADS_K_MAX_TARGETS:
+            return False
+        if K != list(mlps[0])[4].weight.shape[0]:
             return False
     return True
 
 
+HEADS_K_MAX_TARGETS = 16  # x2g_readout_heads_k_max_targets()
+
+
 def readout_mlps(feats, mlps, pool=None):
-    """sum_g mlp_g(feats[g]) -> [R, 1] (see _ReadoutMLPs); with ``pool = (seg_rowptr int32 [S+1], S)`` the
-    rows' sums per segment -> [S, 1] instead (the global add pool after AtomWise, model.py:53, fused into the
+    """sum_g mlp_g(feats[g]) -> [R, K] (see _ReadoutMLPs; K = 1 for the single-target models); with
+    ``pool = (seg_rowptr int32 [S+1], S)`` the rows' sums per segment -> [S, K] instead (the global add pool after AtomWise, model.py:53, fused into the
     head launch each way)."""
     params = []
     for m in mlps:
@@ -2549,6 +2583,22 @@ def error_accum(pred, target, acc):
     if pred.numel() != target.numel():
         raise ValueError(f"{pred.numel()} predictions against {target.numel()} targets")
     call("x2g_error_accum", ptr(pred), ptr(target), pred.numel(), ptr(acc), stream_ptr())
+
+
+def error_accum_cols(pred, target, acc):
+    """``error_accum`` per target: ``pred`` / ``target`` contiguous fp32 [B, K], ``acc`` float64 [K, 4] (zeroed
+    by the caller); row k of ``acc`` takes column k's sum |d|, sum d^2, max |d| and count.  One launch
+    (x2g_error_accum_cols), no allocation, nothing read back."""
+    _need_cuda(pred, target, acc)
+    if pred.dim() != 2 or pred.shape != target.shape:
+        raise ValueError(f"error_accum_cols takes [B, K] predictions and targets, got {tuple(pred.shape)} and "
+                         f"{tuple(target.shape)}")
+    K = pred.shape[1]
+    _acc_ok(acc, 4 * K)
+    for t in (pred, target):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("error_accum_cols takes contiguous fp32 predictions and targets")
+    call("x2g_error_accum_cols", ptr(pred), ptr(target), pred.shape[0], K, ptr(acc), stream_ptr())
 
 
 def weighted_accum(value, weight, acc):

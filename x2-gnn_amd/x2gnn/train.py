@@ -379,7 +379,9 @@ class Evaluator:
             self.swap = ParamSwap(targets, params)  # (checks counts and shapes now, not at the first batch)
         dev = next(model.parameters()).device
         # allocated here, outside any capture: the graph and the eager path add into the same four doubles
-        self.acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        # (a K-target model, ``model.num_target`` = K > 1: one row of four per target, ops.error_accum_cols)
+        self.num_target = int(getattr(model, "num_target", 1))
+        self.acc = torch.zeros((self.num_target, 4) if self.num_target > 1 else 4, dtype=torch.float64, device=dev)
         self.graph = None
         self.out = None
 
@@ -402,7 +404,10 @@ class Evaluator:
         y = batch.y
         if y.dtype != torch.float32 or not y.is_contiguous():
             y = y.to(torch.float32).contiguous()
-        ops.error_accum(e, y, self.acc)
+        if self.num_target > 1:
+            ops.error_accum_cols(e, y.view(e.shape), self.acc)
+        else:
+            ops.error_accum(e, y, self.acc)
         return e
 
     def update(self, batch):
@@ -437,7 +442,21 @@ class Evaluator:
 
     def result(self, std=1.0):
         """The only sync: ``{"mae": std * acc0 / acc3, "rmse": std * sqrt(acc1 / acc3), "max_abs": std * acc2,
-        "count": int(acc3)}`` (``std``: the targets' scale, trainer.py:57)."""
+        "count": int(acc3)}`` (``std``: the targets' scale, trainer.py:57).  A K-target model: ``std`` a number or
+        K numbers, ``mae`` / ``rmse`` / ``max_abs`` lists of K (per target), ``count`` the molecules."""
+        if self.num_target > 1:
+            a = self.acc.cpu().tolist()
+            if a[0][3] <= 0:
+                raise ValueError("nothing was evaluated since the last reset")
+            try:
+                stds = [float(v) for v in std]
+            except TypeError:
+                stds = [float(std)] * self.num_target
+            if len(stds) != self.num_target:
+                raise ValueError(f"{len(stds)} scales for {self.num_target} targets")
+            return {"mae": [s * r[0] / r[3] for s, r in zip(stds, a)],
+                    "rmse": [s * math.sqrt(r[1] / r[3]) for s, r in zip(stds, a)],
+                    "max_abs": [s * r[2] for s, r in zip(stds, a)], "count": int(a[0][3])}
         a = [float(v) for v in self.acc.cpu()]
         if a[3] <= 0:
             raise ValueError("nothing was evaluated since the last reset")

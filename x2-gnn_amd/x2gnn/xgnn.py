@@ -22,13 +22,14 @@ from torch.nn import SiLU
 from . import ops
 from .data import Data
 from .layers import EmbeddingBlock, F_B_2D, Linear, RadialBasis, poly_envelop
-from .model import SBFTransformer, SBFTransformerGlobal
+from .model import SBFTransformer, SBFTransformerGlobal, SBFTransformerMulti
 from .plan import GraphPlan
 
 
 class _XGNNBase(nn.Module):
     def _build(self, trunk, sbf_dim, rbf_dim, in_channels, embedding_size, device):
         self.device = device
+        self.num_target = trunk.num_target  # the width of forward's result ([B] when 1, the multi model apart)
         self.cutoff = 5.0  # xgnn.py:30-33 (envelope, sbf and rbf layers all use 5.0)
         self.AF = SiLU()
         self.emb_block = EmbeddingBlock(embedding_size=embedding_size)
@@ -106,19 +107,34 @@ class _XGNNBase(nn.Module):
 
 class xgnn_poly(_XGNNBase):
     def __init__(self, conv_layers=4, sbf_dim=7, rbf_dim=16, in_channels=256, heads=16, embedding_size=128,
-                 device="cpu", attn_dropout=0.0, dropout_seed=0):
+                 device="cpu", attn_dropout=0.0, dropout_seed=0, num_target=1):
         super().__init__()
         trunk = SBFTransformer(conv_layers=conv_layers, emb_size=embedding_size, sbf_dim=sbf_dim, rbf_dim=rbf_dim,
                                in_channels=in_channels, heads=heads, attn_dropout=attn_dropout,
-                               dropout_seed=dropout_seed)
+                               dropout_seed=dropout_seed, num_target=num_target)
         self._build(trunk, sbf_dim, rbf_dim, in_channels, embedding_size, device)
 
 
 class xgnn_poly_global(_XGNNBase):
     def __init__(self, conv_layers=4, sbf_dim=7, rbf_dim=16, in_channels=256, heads=16, embedding_size=128,
-                 device="cpu", pool_option="mean", attn_dropout=0.0, dropout_seed=0):
+                 device="cpu", pool_option="mean", attn_dropout=0.0, dropout_seed=0, num_target=1):
         super().__init__()
         trunk = SBFTransformerGlobal(conv_layers=conv_layers, emb_size=embedding_size, sbf_dim=sbf_dim,
                                      rbf_dim=rbf_dim, in_channels=in_channels, heads=heads, pool_option=pool_option,
-                                     attn_dropout=attn_dropout, dropout_seed=dropout_seed)
+                                     attn_dropout=attn_dropout, dropout_seed=dropout_seed, num_target=num_target)
+        self._build(trunk, sbf_dim, rbf_dim, in_channels, embedding_size, device)
+
+
+class xgnn_poly_multi(_XGNNBase):
+    """All targets on one trunk (SBFTransformerMulti): ``forward`` returns [B, mol_targets + atom_targets], the
+    ``mol_targets`` per-molecule (intensive) columns first, then the ``atom_targets`` per-atom-summed (extensive)
+    ones, QM9's order for its 12 properties at (6, 6)."""
+
+    def __init__(self, conv_layers=4, sbf_dim=7, rbf_dim=16, in_channels=256, heads=16, embedding_size=128,
+                 device="cpu", atom_targets=6, mol_targets=6, pool_option="mean", attn_dropout=0.0, dropout_seed=0):
+        super().__init__()
+        trunk = SBFTransformerMulti(conv_layers=conv_layers, emb_size=embedding_size, sbf_dim=sbf_dim,
+                                    rbf_dim=rbf_dim, in_channels=in_channels, heads=heads, atom_targets=atom_targets,
+                                    mol_targets=mol_targets, pool_option=pool_option, attn_dropout=attn_dropout,
+                                    dropout_seed=dropout_seed)
         self._build(trunk, sbf_dim, rbf_dim, in_channels, embedding_size, device)
