@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -91,31 +92,12 @@ class LineGraph:
         self.atom_j = torch.empty(self.T, **i32)
         self.atom_i = torch.empty(self.T, **i32)
         self.atom_k = torch.empty(self.T, **i32)
-        self._src_rowptr = None
-        self._src_perm = None
-        self._src_dst = None
+        self._declare_optional()
         self.order_status = None  # built here in order: nothing to check
-        # per-line-node element rows of the x2g_vertex_to_edge line graph (GraphPlan sets them):
-        # dst_type[e] = Z of e's destination atom = the edge row of every triplet into e, and
-        # src_type[s] = Z of s's source atom = the same row for every triplet out of s
-        self.dst_type = self.src_type = None
         ws_bytes = int(_lib.load().x2g_vertex_to_edge_workspace(self.E, self.N))
         self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        # symmetric graphs: each edge's reverse and where its triplet block starts, for the center-atom
-        # attention kernels (written by the same emission grid)
-        self.edge_rev = torch.empty(self.E, **i32) if self.symmetric else None
-        self.rev_trip = torch.empty(self.E, **i32) if self.symmetric else None
-        # degree bound of the center atoms (host metadata; set by GraphPlan, None = unknown) and each atom's
-        # element row (int32 [N]: the key of the center-atom edge-term gradient)
-        self.max_degree = None
-        self.atom_type = None
-        # the center kernels' workgroups (collate's; None: the identity): int32 [N] the atoms by decreasing
-        # degree (one per workgroup), and the fused forward's packs (data.center_packs): int32 [N] the atoms
-        # unit by unit, int32 [P + 1] the units' bounds in it, the largest row count of the units after the
-        # first center_hubs (single atoms of more rows than the fused forward's LDS image holds: the tiled form)
-        self.center_order = self.pack_order = self.center_packs = self.center_rows = self.pack_info = None
-        self.center_hubs = 0
-        self.center_mixed = False  # the schedule is x2g_center_schedule's (hub units among the packs)
+        if self.symmetric:  # (written by the same emission grid)
+            self.edge_rev, self.rev_trip = torch.empty(self.E, **i32), torch.empty(self.E, **i32)
         if molecules is not None:
             mol_ptr, line_ptr, trips, max_atoms = molecules
             call("x2g_vertex_to_edge_sym_mol", ptr(edge_src), ptr(edge_dst), self.E, self.N, self.T, ptr(mol_ptr),
@@ -141,6 +123,34 @@ class LineGraph:
              ptr(self.trip_rowptr), ptr(self.trip_src), ptr(self.trip_dst), ptr(self.atom_j), ptr(self.atom_i),
              ptr(self.atom_k), ptr(self._ws), ws_bytes, stream_ptr())
 
+    def _declare_optional(self):
+        """Every field a line graph may go without, at its empty value (the constructors, GraphPlan, collate's
+        schedules and spherical_basis fill them in)."""
+        self._src_rowptr = self._src_perm = self._src_dst = None  # the by-source lists (src_csr)
+        # per-line-node element rows of the x2g_vertex_to_edge line graph (GraphPlan sets them):
+        # dst_type[e] = Z of e's destination atom = the edge row of every triplet into e, and
+        # src_type[s] = Z of s's source atom = the same row for every triplet out of s
+        self.dst_type = self.src_type = None
+        # degree bound of the center atoms (host metadata; set by GraphPlan, None = unknown) and each atom's
+        # element row (int32 [N]: the key of the center-atom edge-term gradient)
+        self.max_degree = None
+        self.atom_type = None
+        # symmetric graphs: each edge's reverse and where its triplet block starts, for the center-atom
+        # attention kernels
+        self.edge_rev = self.rev_trip = None
+        # the center kernels' workgroups (collate's; None: the identity): int32 [N] the atoms by decreasing
+        # degree (one per workgroup), and the fused forward's packs (data.center_packs): int32 [N] the atoms
+        # unit by unit, int32 [P + 1] the units' bounds in it, the largest row count of the units after the
+        # first center_hubs (single atoms of more rows than the fused forward's LDS image holds: the tiled form)
+        self.center_order = self.pack_order = self.center_packs = self.center_rows = self.pack_info = None
+        self.center_hubs = 0
+        self.center_mixed = False  # the schedule is x2g_center_schedule's (hub units among the packs)
+        # spherical_basis' factors (sbf, rbf_env, Y[T, 8]) and the arguments of its unwritten lazy rows
+        self.sbf_factors = self.sbf_pending = None
+        # host counts per molecule (line nodes, triplets[, atoms]: GraphPlan) and _infer_tiles' lists by tile size
+        self.mol_counts = None
+        self._infer_tile_cache = {}
+
     @classmethod
     def from_triplets(cls, triplet_index, num_line_nodes: int):
         """Wrap an existing triplet index [2, T] whose row 1 is sorted ascending (as vertex_to_edge_2
@@ -154,13 +164,8 @@ class LineGraph:
         lg.trip_src = _i32(triplet_index[0])
         lg.trip_dst = _i32(triplet_index[1])
         lg.trip_rowptr, lg.order_status = csr_rowptr_checked(lg.trip_dst, lg.E)
-        lg._src_rowptr = lg._src_perm = lg._src_dst = None
-        lg.dst_type = lg.src_type = None
         lg.symmetric = False
-        lg.edge_rev = lg.rev_trip = lg.max_degree = lg.atom_type = None
-        lg.center_order = lg.pack_order = lg.center_packs = lg.center_rows = lg.pack_info = None
-        lg.center_hubs = 0
-        lg.center_mixed = False
+        lg._declare_optional()
         ws_bytes = int(_lib.load().x2g_vertex_to_edge_workspace(lg.E, 0))
         lg._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=lg.trip_src.device)
         return lg
@@ -296,7 +301,7 @@ def spherical_basis(pos, lg: LineGraph, rbf_env, want_cos=False, num_spherical: 
     # the factors are kept for the factorised backward and for the fused-projection center forward (which
     # also runs without grad, in inference: its source-tiled form takes every degree up to the center kernels'
     # bound)
-    sf_fits = getattr(lg, "max_degree", None) is not None and lg.max_degree <= CENTER_MAX_DEGREE
+    sf_fits = lg.max_degree is not None and lg.max_degree <= CENTER_MAX_DEGREE
     fold = _FOLD_SBF and (num_spherical, num_radial) == FOLD_BASIS and (torch.is_grad_enabled() or sf_fits)
     ylm = torch.empty(lg.T, 8, dtype=torch.float32, device=pos.device) if fold else None
     # lazy (the model's own forward): only the factors are written; the [T, S] rows are filled by
@@ -319,7 +324,7 @@ LAZY_SBF = True
 def materialize_sbf(lg, sbf):
     """Fill the [T, S] sbf rows a lazy spherical_basis left unwritten, if ``sbf`` is them (every consumer that
     reads sbf values, rather than its factors, calls this first)."""
-    pend = getattr(lg, "sbf_pending", None)
+    pend = lg.sbf_pending
     if pend is None or pend[0] is not sbf:
         return sbf
     out, pos, rbf_env, ns, nr = pend
@@ -341,60 +346,47 @@ def spherical_basis_from_angles(theta, trip_src, rbf_env, num_spherical: int = 7
 
 
 # ---------------------------------------------------------------------------------- attention
-# Graph LayerNorm after the conv (model.py:46) fused: the attention forward leaves per-row (mean, M2)
-# statistics (x2g_sbf_attention_fwd_stats) and the trunk's row chain normalises its input while
-# staging it (x2g_chain_fwd_ln) instead of a LayerNorm pass over the rows.  False: separate.
-#
-# The module switches below (_LN_FUSE, _LN_BWD_ROWS, _SRC_G, _FOLD_SBF, _DEFER_KEYED, INFER_TILE,
-# _CHAIN, _FAN_IN, _POOL_BATCH) are constants, not environment reads: each exists because a parity
-# test flips it to check the fused path against the plain one (tests/test_gpu_model.py,
-# tests/test_gpu_kernels.py).  Paths that were measured slower and had no such test are deleted.
-_LN_FUSE = True
-# With the fused LayerNorm, its backward's per-molecule sums come from per-row sums the chain
-# backward leaves (x2g_chain_bwd_ln + x2g_graph_layernorm_bwd_rows): False = the two-pass LN backward.
-_LN_BWD_ROWS = True
-# The folded source-major pass recomputes g_t = d loss / d a_t (per head) itself — bitwise the value
-# the destination pass computes — so g [T, H] is neither written nor read: False = the round trip.
-_SRC_G = True
-
-# Factorised lin_sbf backward (csrc/attention_fold.inc): False restores the two-pass backward +
-# [T, D] d_sbfproj + T-row weight GEMM (the drop-in conv API takes it anyway: its sbf is an
-# arbitrary [T, 42] tensor).
-_FOLD_SBF = True
 FOLD_BASIS = (7, 6)  # the (num_spherical, num_radial) the folded kernels are compiled for (sbf_dim 42)
-
-
-def _sbf_factors(lg, sbf, edge_mode, D, edge, edge_row):
-    fac = getattr(lg, "sbf_factors", None)
-    if (fac is None or fac[0] is not sbf or edge_mode == EDGE_PER_TRIPLET or D not in (32, 64, 128)
-            or sbf.shape[1] != FOLD_BASIS[0] * FOLD_BASIS[1]):
-        return None
-    if edge_mode == EDGE_PER_DST and (edge_row is None or edge is None or edge.shape[0] > 16):
-        return None  # the source pass stages the per-destination edge table in LDS
-    return fac[1], fac[2]
-
-
 CENTER_MAX_DEGREE = _C["CENTER_MAX_DEGREE"]
-# Center-atom attention kernels (csrc/attention_center.hip) for symmetric line graphs: False = the
-# destination-major kernels everywhere; _CENTER_BWD False = the center forward with the destination-major
-# backward passes (parity tests flip them).
+# the source-tiled forward's dropout instances hold at most 4 destinations per owner (x2g_staged.h)
+DROPOUT_TILED_MAX_DEGREE = 64
+
+# The module switches are constants, not environment reads: each exists because a parity test flips it to check
+# the shipped path against the plain one (paths measured slower and without such a test are deleted).
+# _attention_route reads them at every call.
+#   switch        False selects                                                        flipped by
+#   _LN_FUSE      no per-row (mean, M2) statistics from the attention forward for the  test_fused_variants_
+#                 row chain's fused graph LayerNorm (x2g_chain_fwd_ln): the separate   equal_separate
+#                 LayerNorm kernels after the conv (model.py:46)
+#   _LN_BWD_ROWS  the two-pass LayerNorm backward instead of per-molecule sums from    the same test
+#                 the chain backward's per-row sums (x2g_graph_layernorm_bwd_rows)
+#   _SRC_G        g_t = d loss / d a_t [T, H] written by the destination pass and      the same test
+#                 read by the folded source pass, which otherwise recomputes it
+#   _FOLD_SBF     spherical_basis keeps no factors, so no route has them: the plain    test_factorised_sbf_
+#                 backward + [T, D] d_sbfproj + T-row weight GEMM (the drop-in conv    backward_equals_two_pass
+#                 API takes it anyway: its sbf is any [T, 42] tensor)
+#   _CENTER       the destination-major kernels everywhere                             test_operator_routes
+#   _CENTER_BWD   the center forward with the destination-major backward passes        test_gpu_attention_route.py
+#   _CENTER_SF    S projected first and read (x2g_sbf_project + x2g_sbf_attention_     test_gpu_attention_route.py
+#                 fwd_center) instead of rebuilt from the sbf factors per center atom
+#   _CENTER_P     the fused forward hands the center backward every S row (T x 512 B)  test_operator_routes
+#                 instead of each source's P rows (E x 3.5 KB), from which the
+#                 backward rebuilds S_t = b + sum_l Y_l(t) P_s[l] bit for bit
+#   _PACK_FWD     one atom per workgroup in the fused forward instead of collate's     test_gpu_attention_route.py
+#                 packs (16 owners per workgroup keep 90 % instead of 57 % of them
+#                 busy).  The backward is always one atom per workgroup: packed, its
+#                 phase barriers waited for the longest member (4 % slower, profiles/r5k_*)
+#   INFER_TILE    (a size, below) without grad and with more triplets than this, the   test_inference_tiled_
+#                 S-reading forward runs tile by tile                                  projection_equals_whole
+_LN_FUSE = True
+_LN_BWD_ROWS = True
+_SRC_G = True
+_FOLD_SBF = True
 _CENTER = True
 _CENTER_BWD = True
-# The center forward with lin_sbf fused (x2g_sbf_attention_fwd_center_sf: S_t rebuilt from the sbf factors
-# per center atom, no projection launch, no S read; S rows stored only for a backward): False = project S
-# first and read it (x2g_sbf_project + x2g_sbf_attention_fwd_center).
 _CENTER_SF = True
-
-
-def _center_units(lg, packed):
-    """(order, pack_ptr or None, units, max_rows, atom_info or None) of a whole-batch center kernel: with
-    ``packed`` the batch's packs of atoms (data.center_packs) when it has them, else one atom per
-    workgroup by decreasing degree."""
-    packs = getattr(lg, "center_packs", None)
-    if packed and packs is not None and lg.pack_order is not None and lg.center_rows is not None:
-        return lg.pack_order, packs, int(packs.shape[0]) - 1, max(int(lg.center_rows), 1), \
-            getattr(lg, "pack_info", None)
-    return lg.center_order, None, lg.N, max(int(lg.max_degree), 1), None
+_CENTER_P = True
+_PACK_FWD = True
 
 
 def _center_split(lg):
@@ -405,22 +397,24 @@ def _center_split(lg):
     hubs among the packs) both forms run over all units, each leaving out the other's (skip_rows / max_rows);
     without either (unpacked) every atom is a unit by decreasing degree, all of them tiled when any exceeds
     the bound."""
-    order, packs, units, rows, info = _center_units(lg, _PACK_FWD)
     sf, tiled = "x2g_sbf_attention_fwd_center_sf", "x2g_sbf_attention_fwd_center_sf_tiled"
-    if packs is not None and getattr(lg, "center_mixed", False):
+    packs = lg.center_packs
+    if not _PACK_FWD or packs is None or lg.pack_order is None or lg.center_rows is None:
+        rows = max(int(lg.max_degree), 1)
+        if rows > CENTER_SF_MAX_ROWS:
+            return lg.center_order, None, None, [(tiled, 0, lg.N, lg.max_degree, 0)]
+        return lg.center_order, None, None, [(sf, 0, lg.N, rows, 0)]
+    units, rows = int(packs.shape[0]) - 1, max(int(lg.center_rows), 1)
+    if lg.center_mixed:
         launches = [(sf, 0, units, CENTER_SF_MAX_ROWS, 0)]
         if lg.max_degree > CENTER_SF_MAX_ROWS:
             launches.insert(0, (tiled, 0, units, lg.max_degree, CENTER_SF_MAX_ROWS))
-        return order, packs, info, launches
-    if packs is not None:
-        hubs = int(getattr(lg, "center_hubs", 0) or 0)
+    else:
+        hubs = int(lg.center_hubs or 0)
         launches = [(tiled, 0, hubs, lg.max_degree, 0)] if hubs else []
         if units > hubs:
             launches.append((sf, hubs, units - hubs, rows, 0))
-        return order, packs, info, launches
-    if rows > CENTER_SF_MAX_ROWS:
-        return order, None, None, [(tiled, 0, units, lg.max_degree, 0)]
-    return order, None, None, [(sf, 0, units, rows, 0)]
+    return lg.pack_order, packs, lg.pack_info, launches
 
 
 def center_schedule(atom_rowptr, src_row, num_atoms: int):
@@ -452,61 +446,24 @@ def _center_launch(launches, common, outs, drop=()):
             call(name, *common, u0, n, rows, *outs, *drop)
 
 
-# the source-tiled forward's dropout instances hold at most 4 destinations per owner (x2g_staged.h)
-DROPOUT_TILED_MAX_DEGREE = 64
-
-
-def _dropout_route(lg, edge_mode, edge_row, D, channels, heads, factors, backward):
-    """Attention dropout runs on one route only, the fused center forward and (``backward``) the P-row center
-    backward; anything else raises NotImplementedError naming the condition that failed."""
-    why = None
-    if not (_CENTER and _CENTER_SF and _CENTER_P):
-        why = "the center kernels are switched off (ops._CENTER / _CENTER_SF / _CENTER_P)"
-    elif edge_mode == EDGE_PER_TRIPLET:
-        why = "per-triplet edge_attr (the center kernels take no edge term or one row per destination, edge_row)"
-    elif getattr(lg, "edge_rev", None) is None or lg.max_degree is None:
-        why = "a line graph that is not symmetric (no edge_rev / rev_trip: not built by vertex_to_edge)"
-    elif lg.max_degree > CENTER_MAX_DEGREE:
-        why = f"a degree above CENTER_MAX_DEGREE ({lg.max_degree} > {CENTER_MAX_DEGREE})"
-    elif D != 128 or channels % 4:
-        why = f"heads * channels = {D} (compiled: 128, channels a multiple of 4)"
-    elif lg.max_degree > DROPOUT_TILED_MAX_DEGREE:
-        why = (f"a degree above {DROPOUT_TILED_MAX_DEGREE} ({lg.max_degree}): the source-tiled forward has no "
-               "dropout instance for it")
-    elif not _center_rows(lg, edge_mode, edge_row, D, channels)[0]:
-        why = "edge_row is not the line graph's own destination elements (dst_type)"
-    elif factors is None or factors[1] is None:
-        why = "the sbf factors are absent (sbf is not the line graph's own radial x angular product)"
-    elif not _center_sf_ok(lg, factors, D):
-        why = "a unit beyond the fused center forward's LDS image"
-    elif backward and not _center_bwd_ok(lg, heads):
-        why = ("the P-row center backward does not take this line graph (atom_type absent, T * heads * 8 >= 2^31, or "
-               "the largest block's LDS image above 160 KiB)")
-    if why is not None:
-        raise NotImplementedError(f"attention dropout is compiled for the center kernels only: {why}")
-
-
-# Workgroup packs (data.center_packs) in the fused forward: 16 owners per workgroup keep 90 % instead of
-# 57 % of them busy, and its owners never wait for one another (no barrier after the P products).  The
-# backward stays one atom per workgroup on 4 waves: with packs (8 waves) its phase barriers waited for
-# the longest member's owners and it measured 4 % slower (profiles/r5k_*); the packed backward was removed.
-_PACK_FWD = True
-# The fused forward hands the center backward each source's P rows (E x 3.5 KB) instead of every S row
-# (T x 512 B), and the backward rebuilds S_t = b + sum_l Y_l(t) P_s[l] bit for bit: False = S rows.
-_CENTER_P = True
-
-
 def _unit_rows_lds(rows):  # csrc/attention_center.hip unit_rows_lds
     return ((3 * rows + 2 * 32 + 4) * 4 + 15) // 16 * 16
 
 
-def _center_sf_ok(lg, factors, D):
-    """Whether the fused-projection center forward applies: the sbf factors are this call's (the units of more
-    rows than its LDS image holds take its source-tiled form)."""
+def _center_sf_split(lg, factors, D):
+    """_center_split(lg) when the fused-projection center forward applies, else None: the sbf factors are this
+    call's and every untiled launch's LDS image fits (the units of more rows than the untiled form's bound take
+    its source-tiled form)."""
     if not (_CENTER_SF and factors is not None and factors[1] is not None and D == 128 and lg.max_degree is not None):
-        return False
-    _, _, _, launches = _center_split(lg)
-    return all(e.endswith("_tiled") or _unit_rows_lds(r) + 4776 * r <= 160 * 1024 for e, _, _, r, _ in launches)
+        return None
+    split = _center_split(lg)
+    fits = all(e.endswith("_tiled") or _unit_rows_lds(r) + 4776 * r <= 160 * 1024 for e, _, _, r, _ in split[3])
+    return split if fits else None
+
+
+def _center_sf_ok(lg, factors, D):
+    """Whether the fused-projection center forward applies (_center_sf_split)."""
+    return _center_sf_split(lg, factors, D) is not None
 
 
 def _center_bwd_ok(lg, heads, s_rows=False):
@@ -523,7 +480,7 @@ def _center_rows(lg, edge_mode, edge_row, D, channels):
     """(ok, src_row): whether the center-atom forward applies to this call, and the per-source edge-table
     row it reads for EDGE_PER_DST (the center atom's element: lg.src_type, valid when the caller's
     per-destination rows are the line graph's own dst_type)."""
-    if (not _CENTER or getattr(lg, "edge_rev", None) is None or lg.max_degree is None
+    if (not _CENTER or lg.edge_rev is None or lg.max_degree is None
             or lg.max_degree > CENTER_MAX_DEGREE or D != 128 or channels % 4 or edge_mode == EDGE_PER_TRIPLET):
         return False, None
     if edge_mode == EDGE_PER_DST:
@@ -533,84 +490,185 @@ def _center_rows(lg, edge_mode, edge_row, D, channels):
     return True, None
 
 
+class _Route(NamedTuple):
+    """Which attention kernels one sbf_attention call runs and what its forward keeps (_attention_route)."""
+    factors: Optional[tuple]  # (radial [E, 42], Y [T, 8]) when sbf is their product and the folded kernels take it
+    src_row: object  # the center kernels' per-source edge-table row (EDGE_PER_DST), else None
+    forward: str  # "fused" (lin_sbf inside the center forward) | "center" | "dst" (both read S rows)
+    order: object  # fused: _center_split's units ...
+    packs: object
+    info: object
+    launches: Optional[list]  # ... and the launches that cover them
+    tiles: Optional[list]  # the S-reading forward's inference tiles (_infer_tiles); None: all rows at once
+    backward: Optional[str]  # None (no backward follows) | "center_p" | "center_s" | "dst_fold" | "dst_plain"
+    alpha: bool  # the forward writes the logits [T, H]
+    sproj: bool  # ... the S rows [T, D] (tiled: one tile's)
+    sbf_p: bool  # ... the sources' P rows [E, 7, D]
+    rstats: bool  # ... the per-row (mean, M2) of the output, for a graph LayerNorm fused into the next row chain
+    reads_sbf: bool  # the sbf rows themselves are read (materialize_sbf), not only their factors
+    dropout_refusal: Optional[str]  # with dropout: None when this route has the staged dropout entries, else why not
+
+
+def _attention_route(lg, edge_mode, edge_rows, edge_row, heads, channels, own_sbf, sbf_dim, keeps, keep_alpha,
+                     dropout, grad_enabled):
+    """The one decision of which kernels an sbf_attention call runs, from the line graph, the call's shape and the
+    switches in the table above as they stand now (nothing is cached: tests flip a switch between two calls).
+    ``edge_rows``: the edge table's row count (None without one); ``own_sbf``: sbf is lg.sbf_factors' product;
+    ``keeps``: a backward will follow; ``keep_alpha``: the caller wants the logits; ``dropout``: it is set.
+
+    Forward: the fused center forward where the center kernels take the call (_center_rows), the factors are the
+    call's and the launches fit (_center_sf_split); else S = lin_sbf(sbf) is projected once per layer, right before
+    the attention kernel reads its rows, by the center forward or else the destination-major one — tile by tile
+    without grad beyond INFER_TILE triplets.  Backward: without factors the plain destination-major passes;
+    with them the center backward from the fused forward's P rows, else from S rows, else the destination-major
+    fold passes.  The logits are stored for a caller who wants them and for every backward but the P-row one,
+    which recomputes them from rows it stages (the center forwards skip the store otherwise: 223 MB per layer
+    in config 5's inference, 12 MB written and read back per layer in config 2's training)."""
+    D = heads * channels
+    factors = None
+    if (own_sbf and edge_mode != EDGE_PER_TRIPLET and D in (32, 64, 128) and sbf_dim == FOLD_BASIS[0] * FOLD_BASIS[1]
+            # (the folded source pass stages the per-destination edge table in LDS)
+            and not (edge_mode == EDGE_PER_DST and (edge_row is None or edge_rows is None or edge_rows > 16))):
+        factors = lg.sbf_factors[1], lg.sbf_factors[2]
+    center, src_row = _center_rows(lg, edge_mode, edge_row, D, channels)
+    split = _center_sf_split(lg, factors, D) if center else None
+    fused = split is not None
+    backward = None
+    if keeps and factors is None:
+        backward = "dst_plain"
+    elif keeps and fused and _CENTER_P and _center_bwd_ok(lg, heads):
+        backward = "center_p"
+    elif keeps:
+        backward = "center_s" if center and _center_bwd_ok(lg, heads, s_rows=True) else "dst_fold"
+    refusal = None
+    if dropout:
+        refusal = _dropout_refusal(lg, edge_mode, D, channels, center, factors, fused, keeps and backward != "center_p")
+    tiles = None
+    if not (fused or dropout or grad_enabled) and lg.T > INFER_TILE and lg.E > 0:
+        tiles = _infer_tiles(lg, INFER_TILE)
+        # whole molecules: a tile's atoms own exactly its triplets, so the center forward can take it
+        center = center and all(t[4] is not None for t in tiles)
+    return _Route(factors, src_row, "fused" if fused else "center" if center else "dst", *(split or (None,) * 4),
+                  tiles, backward, alpha=keep_alpha or not center or (keeps and backward != "center_p"),
+                  sproj=not fused or backward in ("center_s", "dst_fold"), sbf_p=backward == "center_p",
+                  rstats=_LN_FUSE and D == 128, reads_sbf=not fused, dropout_refusal=refusal)
+
+
+def _dropout_refusal(lg, edge_mode, D, channels, center, factors, fused, no_p_backward):
+    """Attention dropout runs on one route only, the fused center forward and the P-row center backward: None
+    for it, else the first condition that fails."""
+    if not (_CENTER and _CENTER_SF and _CENTER_P):
+        return "the center kernels are switched off (ops._CENTER / _CENTER_SF / _CENTER_P)"
+    if edge_mode == EDGE_PER_TRIPLET:
+        return "per-triplet edge_attr (the center kernels take no edge term or one row per destination, edge_row)"
+    if lg.edge_rev is None or lg.max_degree is None:
+        return "a line graph that is not symmetric (no edge_rev / rev_trip: not built by vertex_to_edge)"
+    if lg.max_degree > CENTER_MAX_DEGREE:
+        return f"a degree above CENTER_MAX_DEGREE ({lg.max_degree} > {CENTER_MAX_DEGREE})"
+    if D != 128 or channels % 4:
+        return f"heads * channels = {D} (compiled: 128, channels a multiple of 4)"
+    if lg.max_degree > DROPOUT_TILED_MAX_DEGREE:
+        return (f"a degree above {DROPOUT_TILED_MAX_DEGREE} ({lg.max_degree}): the source-tiled forward has no "
+                "dropout instance for it")
+    if not center:
+        return "edge_row is not the line graph's own destination elements (dst_type)"
+    if factors is None or factors[1] is None:
+        return "the sbf factors are absent (sbf is not the line graph's own radial x angular product)"
+    if not fused:
+        return "a unit beyond the fused center forward's LDS image"
+    if no_p_backward:
+        return ("the P-row center backward does not take this line graph (atom_type absent, T * heads * 8 >= 2^31, or "
+                "the largest block's LDS image above 160 KiB)")
+    return None
+
+
+def _off(t, nbytes):
+    return None if t is None else t.data_ptr() + nbytes
+
+
+def _attention_forward(route, q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode, edge_row, heads, channels,
+                       drop=()):
+    """The route's forward launches: (the fp32 operands a backward saves, (out, alpha, smax, sden, rstats), the
+    S rows, the P rows).  ``drop``: _center_launch's."""
+    q, k, v, skip = _f32(q), _f32(k), _f32(v), _f32(skip)
+    sbf, w_sbf, b_sbf = _f32(sbf), _f32(w_sbf), _f32(b_sbf)
+    edge = _f32(edge) if edge is not None else None
+    E, T, D, H = q.shape[0], lg.T, heads * channels, heads
+    f32 = dict(dtype=torch.float32, device=q.device)
+    out = torch.empty(E, D, **f32)
+    alpha = torch.empty(T, H, **f32) if route.alpha else None
+    smax, sden = torch.empty(E, H, **f32), torch.empty(E, H, **f32)
+    rstats = torch.empty(E, 2, **f32) if route.rstats else None
+    sproj = sbf_p = None
+    st = stream_ptr()
+    if route.reads_sbf:
+        materialize_sbf(lg, sbf)
+    if route.forward == "fused":
+        if route.sbf_p:
+            sbf_p = torch.empty(E, 7, D, **f32)
+        elif route.sproj:
+            sproj = torch.empty(T, D, **f32)
+        common = (ptr(q), ptr(k), ptr(v), ptr(skip), ptr(edge), ptr(route.src_row), edge_mode, ptr(route.factors[0]),
+                  ptr(route.factors[1]), ptr(w_sbf), ptr(b_sbf), ptr(lg.atom_rowptr), ptr(lg.edge_rev),
+                  ptr(lg.rev_trip), ptr(route.order), ptr(route.packs), ptr(route.info))
+        outs = (E, T, heads, channels, ptr(out), ptr(alpha), ptr(smax), ptr(sden), ptr(rstats), ptr(sproj),
+                ptr(sbf_p), st)
+        _center_launch(route.launches, common, outs, drop)
+        return (q, k, v, edge, sbf, b_sbf), (out, alpha, smax, sden, rstats), sproj, sbf_p
+    # S = lin_sbf(sbf) [T, D] (or one tile's rows of it) right before the attention kernel reads them (so they
+    # are still in the MALL: sbf pointer = S, weight pointer NULL) instead of re-projecting per triplet
+    whole = route.tiles is None
+    tiles = [(0, E, 0, T, (0, lg.N))] if whole else route.tiles
+    sproj = torch.empty(max(t[3] - (t[2] & ~1) for t in tiles), D, **f32)
+    fb, ib = 4, 4  # bytes per float32 / int32 element
+    for e0, e1, t0, t1, atoms in tiles:
+        ta = t0 & ~1  # from an even row: the projection's fast path wants 16-byte aligned sbf blocks
+        call("x2g_sbf_project", _off(sbf, ta * sbf.shape[1] * fb), t1 - ta, sbf.shape[1], ptr(w_sbf), ptr(b_sbf), D,
+             ptr(sproj), st)
+        if route.forward == "center":  # the tile's atoms own exactly its triplets (S rows t - ta)
+            call("x2g_sbf_attention_fwd_center", ptr(q), ptr(k), ptr(v), ptr(skip), ptr(edge), ptr(route.src_row),
+                 edge_mode, ptr(sproj), ta, ptr(lg.atom_rowptr), ptr(lg.edge_rev), ptr(lg.rev_trip),
+                 ptr(lg.center_order) if whole else None, atoms[0], atoms[1] - atoms[0], lg.max_degree, E, T, heads,
+                 channels, ptr(out), ptr(alpha), ptr(smax), ptr(sden), ptr(rstats), st)
+            continue
+        # the kernel reads S at absolute triplet indices t in [t0, t1): hand it the base S - ta rows;
+        # everything per destination edge is offset by e0, everything per triplet / per source edge
+        # is indexed absolutely (edge: a table under edge_row, else one row per destination edge)
+        e_edge = _off(edge, e0 * D * fb) if edge_mode == EDGE_PER_DST and edge_row is None else ptr(edge)
+        e_row = _off(edge_row, e0 * ib) if whole or edge_mode == EDGE_PER_DST else None
+        call("x2g_sbf_attention_fwd_stats" if rstats is not None else "x2g_sbf_attention_fwd",
+             _off(q, e0 * D * fb), ptr(k), ptr(v), _off(skip, e0 * D * fb), e_edge, e_row, edge_mode,
+             _off(sproj, -ta * D * fb), None, None, _off(lg.trip_rowptr, e0 * ib), ptr(lg.trip_src), e1 - e0, T, heads,
+             channels, D, _off(out, e0 * D * fb), ptr(alpha), _off(smax, e0 * H * fb), _off(sden, e0 * H * fb),
+             *((_off(rstats, e0 * 2 * fb),) if rstats is not None else ()), st)
+    return (q, k, v, edge, sbf, b_sbf), (out, alpha, smax, sden, rstats), sproj, sbf_p
+
+
 class _SBFAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode, edge_row, heads, channels,
-                keep_alpha=True, dropout=None):
-        w_param, b_param = w_sbf, b_sbf
+    def forward(ctx, q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode, edge_row, heads, channels, route,
+                dropout=None):
         # its gradient is read only by the table chain's backward, which flushes deferred sums first
         pending = getattr(edge, "_x2g_keyed_pending", None)
         ctx.defer_edge = _DEFER_KEYED and pending is not None and ctx.needs_input_grad[4]
         ctx.keyed_pending = pending
-        factors = _sbf_factors(lg, sbf, edge_mode, heads * channels, edge, edge_row)
-        q, k, v, skip = _f32(q), _f32(k), _f32(v), _f32(skip)
-        sbf, w_sbf, b_sbf = _f32(sbf), _f32(w_sbf), _f32(b_sbf)
-        edge = _f32(edge) if edge is not None else None
-        E, T, D = q.shape[0], lg.T, heads * channels
-        dev = q.device
-        out = torch.empty(E, D, dtype=torch.float32, device=dev)
-        center, src_row = _center_rows(lg, edge_mode, edge_row, D, channels)
-        # attention dropout (p, key int64 [2] on the device, salt): the staged entries, on the one route they
-        # cover; the backward regenerates the mask from the key saved here
+        # attention dropout (p, key int64 [2] on the device, salt): the staged entries; the backward regenerates
+        # the mask from the key saved here
         drop, drop_key = (), None
         if dropout is not None:
-            _dropout_route(lg, edge_mode, edge_row, D, channels, heads, factors, _keeps(ctx))
             drop_key = dropout[1]
             drop = (float(dropout[0]), ptr(drop_key), int(dropout[2]))
         ctx.dropout = None if dropout is None else (drop[0], drop[2])
-        # the P-row center backward (the shipped training path) recomputes the logits from rows it stages
-        p_bwd = center and _CENTER_P and _center_sf_ok(lg, factors, D) and _center_bwd_ok(lg, heads)
-        # the logits [T, H] are read by the other backwards or for the attention weights; the center forwards
-        # skip the store otherwise (inference: 223 MB per layer at config 5; training: 12 MB written and read
-        # back per layer at config 2)
-        alpha = (torch.empty(T, heads, dtype=torch.float32, device=dev)
-                 if keep_alpha or not center or (_keeps(ctx) and not p_bwd) else None)
-        smax = torch.empty(E, heads, dtype=torch.float32, device=dev)
-        sden = torch.empty(E, heads, dtype=torch.float32, device=dev)
-        # per-row (mean, M2) of the output for a graph LayerNorm fused into the next row chain
-        rstats = torch.empty(E, 2, dtype=torch.float32, device=dev) if _LN_FUSE and D == 128 else None
-        sbf_p = None
-        if center and _center_sf_ok(lg, factors, D):
-            # lin_sbf fused into the center forward: S_t rebuilt per center atom from the sbf factors; for a
-            # backward, the sources' P rows (the center backward rebuilds S_t from them) or the S rows
-            sproj = None
-            if _keeps(ctx):
-                if p_bwd:
-                    sbf_p = torch.empty(E, 7, D, dtype=torch.float32, device=dev)
-                else:
-                    sproj = torch.empty(T, D, dtype=torch.float32, device=dev)
-            # (the atoms beyond the untiled form's LDS image take the source-tiled form: _center_split)
-            order, packs, info, launches = _center_split(lg)
-            common = (ptr(q), ptr(k), ptr(v), ptr(skip), ptr(edge), ptr(src_row), edge_mode, ptr(factors[0]),
-                      ptr(factors[1]), ptr(w_sbf), ptr(b_sbf), ptr(lg.atom_rowptr), ptr(lg.edge_rev),
-                      ptr(lg.rev_trip), ptr(order), ptr(packs), ptr(info))
-            outs = (E, T, heads, channels, ptr(out), ptr(alpha), ptr(smax), ptr(sden), ptr(rstats), ptr(sproj),
-                    ptr(sbf_p), stream_ptr())
-            _center_launch(launches, common, outs, drop)
-        else:
-            # S = lin_sbf(sbf) once per layer [T, D], right before this layer's attention (so it is still
-            # in the MALL when the attention kernels read its rows: sbf pointer = S, weight pointer NULL)
-            # instead of re-projecting per triplet
-            sproj = torch.empty(T, D, dtype=torch.float32, device=dev)
-            materialize_sbf(lg, sbf)
-            call("x2g_sbf_project", ptr(sbf), T, sbf.shape[1], ptr(w_sbf), ptr(b_sbf), D, ptr(sproj), stream_ptr())
-            if center:
-                call("x2g_sbf_attention_fwd_center", ptr(q), ptr(k), ptr(v), ptr(skip), ptr(edge), ptr(src_row),
-                     edge_mode, ptr(sproj), 0, ptr(lg.atom_rowptr), ptr(lg.edge_rev), ptr(lg.rev_trip),
-                     ptr(lg.center_order), 0, lg.N, lg.max_degree, E, T, heads, channels, ptr(out), ptr(alpha),
-                     ptr(smax), ptr(sden), ptr(rstats), stream_ptr())
-            else:
-                call("x2g_sbf_attention_fwd_stats" if rstats is not None else "x2g_sbf_attention_fwd", ptr(q),
-                     ptr(k), ptr(v), ptr(skip), ptr(edge), ptr(edge_row), edge_mode, ptr(sproj), None, None,
-                     ptr(lg.trip_rowptr), ptr(lg.trip_src), E, T, heads, channels, D, ptr(out), ptr(alpha),
-                     ptr(smax), ptr(sden), *((ptr(rstats),) if rstats is not None else ()), stream_ptr())
-        if factors is not None:  # the factorised backward never reads sbf itself
-            ctx.save_for_backward(q, k, v, edge, factors[0], factors[1], sproj, alpha, smax, sden, sbf_p,
-                                  b_sbf if sbf_p is not None else None, drop_key)
+        (q, k, v, edge, sbf, b_f32), outs, sproj, sbf_p = _attention_forward(
+            route, q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode, edge_row, heads, channels, drop)
+        out, alpha, smax, sden, rstats = outs
+        if route.factors is not None:  # the factorised backward never reads sbf itself
+            ctx.save_for_backward(q, k, v, edge, *route.factors, sproj, alpha, smax, sden, sbf_p,
+                                  b_f32 if sbf_p is not None else None, drop_key)
         else:
             ctx.save_for_backward(q, k, v, edge, sbf, None, sproj, alpha, smax, sden, None, None, None)
-        ctx.fold = factors is not None
-        ctx.w_param, ctx.b_param = w_param, b_param
+        ctx.route = route
+        ctx.w_param, ctx.b_param = w_sbf, b_sbf
         ctx.lg, ctx.edge_mode, ctx.edge_row, ctx.heads, ctx.channels = lg, edge_mode, edge_row, heads, channels
         ctx.edge_shape = None if edge is None else edge.shape
         # (one call: a second mark_non_differentiable replaces the first's set)
@@ -622,72 +680,56 @@ class _SBFAttention(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, _da=None, _dm=None, _ds=None, _dr=None):
+        # (with factors, the saved sbf is the radial factor rbf_env [E, 42])
         q, k, v, edge, sbf, ylm, sproj, alpha, smax, sden, sbf_p, b_sbf, drop_key = ctx.saved_tensors
-        lg, mode, heads, channels = ctx.lg, ctx.edge_mode, ctx.heads, ctx.channels
+        lg, mode, heads, channels, form = ctx.lg, ctx.edge_mode, ctx.heads, ctx.channels, ctx.route.backward
         dout = _f32(dout)
         E, T, D = q.shape[0], lg.T, heads * channels
-        dev = q.device
-        dq = torch.empty(E, D, dtype=torch.float32, device=dev)
-        dk = torch.empty_like(dq)
-        dv = torch.empty_like(dq)
-        if ctx.fold:  # sbf here is the radial factor rbf_env [E, 42]
-            return _SBFAttention._backward_fold(ctx, dout, q, k, v, edge, sbf, ylm, sproj, alpha, smax, sden, dq, dk, dv,
-                                                sbf_p, b_sbf, drop_key)
-        dlogit = torch.empty(T, heads, dtype=torch.float32, device=dev)
-        dproj = torch.empty(T, D, dtype=torch.float32, device=dev)
-        if mode == EDGE_PER_TRIPLET:
-            d_edge = torch.empty(T, D, dtype=torch.float32, device=dev)
-        elif mode == EDGE_PER_DST:
-            d_edge = torch.empty(E, D, dtype=torch.float32, device=dev)
-        else:
-            d_edge = None
+        f32 = dict(dtype=torch.float32, device=q.device)
+        dq, dk, dv = torch.empty(E, D, **f32), torch.empty(E, D, **f32), torch.empty(E, D, **f32)
         st = stream_ptr()
-        call("x2g_sbf_attention_bwd_dst", ptr(q), ptr(k), ptr(v), ptr(edge), ptr(ctx.edge_row), mode, ptr(sproj),
-             None, None, ptr(lg.trip_rowptr), ptr(lg.trip_src), ptr(alpha), ptr(smax), ptr(sden), ptr(dout), E, T,
-             heads, channels, D, ptr(dq), ptr(d_edge), ptr(dlogit), ptr(dproj), st)
-        src_rowptr, src_perm = lg.src_csr()
-        call("x2g_sbf_attention_bwd_src", ptr(q), ptr(sproj), None, None, ptr(src_rowptr), ptr(src_perm),
-             ptr(lg.trip_dst), ptr(alpha), ptr(smax), ptr(sden), ptr(dlogit), ptr(dout), E, T, heads, channels, D,
-             ptr(dk), ptr(dv), st)
-        if not ctx.needs_input_grad[4]:
-            d_edge = None
-        elif mode == EDGE_PER_DST and ctx.edge_row is not None:
-            # rows of the edge table are shared by many destinations: sum d_edge per table row
-            d_edge = keyed_row_sum(d_edge, ctx.edge_row, ctx.edge_shape[0])
-        materialize_sbf(lg, sbf)
-        # lin_sbf's dW / db (None where summed into the gradient bucket)
-        dw, db = linear_wgrad(dproj, sbf, w_param=ctx.w_param, b_param=ctx.b_param)
-        return dq, dk, dv, dout, d_edge, None, dw, db, None, None, None, None, None, None, None
-
-    @staticmethod
-    def _backward_fold(ctx, dout, q, k, v, edge, radial, ylm, sproj, alpha, smax, sden, dq, dk, dv, sbf_p=None,
-                       b_sbf=None, drop_key=None):
-        lg, mode, heads, channels = ctx.lg, ctx.edge_mode, ctx.heads, ctx.channels
-        E, T, D = q.shape[0], lg.T, heads * channels
-        dev = q.device
-        # g[T, H] (d loss / d a_t): the source pass recomputes it from rows it holds anyway (_SRC_G)
-        g = None if _SRC_G else torch.empty(T, heads, dtype=torch.float32, device=dev)
-        prob = torch.empty(T, heads, dtype=torch.float32, device=dev)
-        rho = torch.empty(E, heads, dtype=torch.float32, device=dev)
-        gfold = torch.empty(E, 8, D, dtype=torch.float32, device=dev)
-        st = stream_ptr()
-        center, src_row = _center_rows(lg, mode, ctx.edge_row, D, channels)
-        if sbf_p is not None or (center and _center_bwd_ok(lg, heads, s_rows=True)):
+        if form == "dst_plain":
+            dlogit = torch.empty(T, heads, **f32)
+            dproj = torch.empty(T, D, **f32)
+            rows = {EDGE_PER_TRIPLET: T, EDGE_PER_DST: E}.get(mode)  # the edge term's gradient: per triplet / destination
+            d_edge = None if rows is None else torch.empty(rows, D, **f32)
+            call("x2g_sbf_attention_bwd_dst", ptr(q), ptr(k), ptr(v), ptr(edge), ptr(ctx.edge_row), mode, ptr(sproj),
+                 None, None, ptr(lg.trip_rowptr), ptr(lg.trip_src), ptr(alpha), ptr(smax), ptr(sden), ptr(dout), E, T,
+                 heads, channels, D, ptr(dq), ptr(d_edge), ptr(dlogit), ptr(dproj), st)
+            src_rowptr, src_perm = lg.src_csr()
+            call("x2g_sbf_attention_bwd_src", ptr(q), ptr(sproj), None, None, ptr(src_rowptr), ptr(src_perm),
+                 ptr(lg.trip_dst), ptr(alpha), ptr(smax), ptr(sden), ptr(dlogit), ptr(dout), E, T, heads, channels, D,
+                 ptr(dk), ptr(dv), st)
+            if not ctx.needs_input_grad[4]:
+                d_edge = None
+            elif mode == EDGE_PER_DST and ctx.edge_row is not None:
+                # rows of the edge table are shared by many destinations: sum d_edge per table row
+                d_edge = keyed_row_sum(d_edge, ctx.edge_row, ctx.edge_shape[0])
+            materialize_sbf(lg, sbf)
+            # lin_sbf's dW / db (None where summed into the gradient bucket)
+            dw, db = linear_wgrad(dproj, sbf, w_param=ctx.w_param, b_param=ctx.b_param)
+            return dq, dk, dv, dout, d_edge, None, dw, db, None, None, None, None, None, None, None
+        gfold = torch.empty(E, 8, D, **f32)
+        if form in ("center_p", "center_s"):
             # one launch for both passes, per center atom (csrc/attention_center.hip); the edge term's
             # gradient comes per center atom and is summed by the atoms' elements
             want_edge = mode == EDGE_PER_DST and ctx.needs_input_grad[4]
-            d_edge = torch.empty(lg.N, D, dtype=torch.float32, device=dev) if want_edge else None
-            g_work = torch.empty(2, T, heads, dtype=torch.float32, device=dev)
+            d_edge = torch.empty(lg.N, D, **f32) if want_edge else None
+            g_work = torch.empty(2, T, heads, **f32)
             # (with dropout: the forward's p, salt and key — the mask is regenerated, never stored)
             drop = () if ctx.dropout is None else (ctx.dropout[0], ptr(drop_key), ctx.dropout[1])
             call("x2g_sbf_attention_bwd_center_drop" if drop else "x2g_sbf_attention_bwd_center", ptr(q), ptr(k),
-                 ptr(v), ptr(edge), ptr(src_row), mode, ptr(sproj),
-                 ptr(sbf_p), ptr(b_sbf), ptr(ylm), ptr(lg.atom_rowptr), ptr(lg.edge_rev), ptr(lg.rev_trip), ptr(lg.center_order),
-                 ptr(alpha), ptr(smax), ptr(sden), ptr(dout), lg.N, lg.max_degree, E, T, heads, channels, ptr(dq),
-                 ptr(dk), ptr(dv), ptr(gfold), ptr(d_edge), ptr(g_work), st, *drop)
-            key = lg.atom_type  # d_edge per center atom: summed by the atoms' elements
-        else:
-            d_edge = torch.empty(E, D, dtype=torch.float32, device=dev) if mode == EDGE_PER_DST else None
+                 ptr(v), ptr(edge), ptr(ctx.route.src_row), mode, ptr(sproj), ptr(sbf_p), ptr(b_sbf), ptr(ylm),
+                 ptr(lg.atom_rowptr), ptr(lg.edge_rev), ptr(lg.rev_trip), ptr(lg.center_order), ptr(alpha), ptr(smax),
+                 ptr(sden), ptr(dout), lg.N, lg.max_degree, E, T, heads, channels, ptr(dq), ptr(dk), ptr(dv),
+                 ptr(gfold), ptr(d_edge), ptr(g_work), st, *drop)
+            key = lg.atom_type
+        else:  # "dst_fold"
+            # g[T, H] (d loss / d a_t): the source pass recomputes it from rows it holds anyway (_SRC_G)
+            g = None if _SRC_G else torch.empty(T, heads, **f32)
+            prob = torch.empty(T, heads, **f32)
+            rho = torch.empty(E, heads, **f32)
+            d_edge = torch.empty(E, D, **f32) if mode == EDGE_PER_DST else None
             call("x2g_sbf_attention_bwd_dst_g", ptr(q), ptr(k), ptr(v), ptr(edge), ptr(ctx.edge_row), mode, ptr(sproj),
                  ptr(lg.trip_rowptr), ptr(lg.trip_src), ptr(alpha), ptr(smax), ptr(sden), ptr(dout), E, T, heads,
                  channels, ptr(dq), ptr(d_edge), ptr(g), ptr(prob), ptr(rho), st)
@@ -708,7 +750,7 @@ class _SBFAttention(torch.autograd.Function):
             else:
                 d_edge = keyed_row_sum(d_edge, key, ctx.edge_shape[0])
         # lin_sbf's dW / db (None where summed into the gradient bucket)
-        dw, db = sbf_radial_wgrad(gfold, radial, ctx.w_param, ctx.b_param)
+        dw, db = sbf_radial_wgrad(gfold, sbf, ctx.w_param, ctx.b_param)
         return dq, dk, dv, dout, d_edge, None, dw, db, None, None, None, None, None, None, None
 
 
@@ -1072,15 +1114,16 @@ INFER_TILE = 1 << 24
 
 
 def _infer_tiles(lg, tmax):
-    """[(e0, e1, t0, t1)] destination-edge ranges of at most ``tmax`` triplets each (a longer
+    """[(e0, e1, t0, t1, atoms)] destination-edge ranges of at most ``tmax`` triplets each (a longer
     segment gets a range of its own), cached on the line graph.  With the batch's per-molecule
     counts (``lg.mol_counts``, set by GraphPlan from host metadata) the ranges are whole molecules,
     found without touching the device, so a captured graph can be recorded from a fresh line
-    graph; otherwise (the drop-in conv API) from the row pointer, read back once."""
-    cache = lg.__dict__.setdefault("_x2g_infer_tiles", {})
+    graph (``atoms``: the range's atoms when the counts give them, else None); otherwise (the drop-in
+    conv API) from the row pointer, read back once."""
+    cache = lg._infer_tile_cache
     if tmax in cache:
         return cache[tmax]
-    counts = getattr(lg, "mol_counts", None)
+    counts = lg.mol_counts
     ap = None
     if counts is not None:
         ec, tc = counts[0], counts[1]
@@ -1111,50 +1154,6 @@ def _infer_tiles(lg, tmax):
     return tiles
 
 
-def _attention_fwd_tiled(q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode, edge_row, heads, channels, tmax,
-                         keep_alpha=True):
-    q, k, v, skip = _f32(q), _f32(k), _f32(v), _f32(skip)
-    sbf, w_sbf, b_sbf = _f32(sbf), _f32(w_sbf), _f32(b_sbf)
-    edge = _f32(edge) if edge is not None else None
-    E, T, D, H = q.shape[0], lg.T, heads * channels, heads
-    f32 = dict(dtype=torch.float32, device=q.device)
-    out = torch.empty(E, D, **f32)
-    smax, sden = torch.empty(E, H, **f32), torch.empty(E, H, **f32)
-    rstats = torch.empty(E, 2, **f32) if _LN_FUSE and D == 128 else None
-    tiles = _infer_tiles(lg, tmax)
-    materialize_sbf(lg, sbf)
-    S = torch.empty(max(t[3] - (t[2] & ~1) for t in tiles), D, **f32)
-    st = stream_ptr()
-    fb, ib = 4, 4  # bytes per float32 / int32 element
-    center, src_row = _center_rows(lg, edge_mode, edge_row, D, channels)
-    center = center and all(t[4] is not None for t in tiles)
-    alpha = torch.empty(T, H, **f32) if keep_alpha or not center else None  # (the center forward may skip it)
-    for e0, e1, t0, t1, atoms in tiles:
-        ta = t0 & ~1  # from an even row: the projection's fast path wants 16-byte aligned sbf blocks
-        call("x2g_sbf_project", sbf.data_ptr() + ta * sbf.shape[1] * fb, t1 - ta, sbf.shape[1], ptr(w_sbf),
-             ptr(b_sbf), D, ptr(S), st)
-        if center:  # whole molecules: the tile's atoms own exactly its triplets (S rows t - ta)
-            call("x2g_sbf_attention_fwd_center", ptr(q), ptr(k), ptr(v), ptr(skip), ptr(edge), ptr(src_row), edge_mode,
-                 ptr(S), ta, ptr(lg.atom_rowptr), ptr(lg.edge_rev), ptr(lg.rev_trip), None, atoms[0], atoms[1] - atoms[0],
-                 lg.max_degree, E, T, heads, channels, ptr(out), ptr(alpha), ptr(smax), ptr(sden), ptr(rstats), st)
-            continue
-        # the kernel reads S at absolute triplet indices t in [t0, t1): hand it the base S - ta rows;
-        # everything per destination edge is offset by e0, everything per triplet / per source edge
-        # is indexed absolutely
-        if edge_mode == EDGE_PER_DST:
-            e_edge = ptr(edge) if edge_row is not None else edge.data_ptr() + e0 * D * fb
-            e_row = edge_row.data_ptr() + e0 * ib if edge_row is not None else None
-        else:
-            e_edge, e_row = ptr(edge), None
-        call("x2g_sbf_attention_fwd_stats" if rstats is not None else "x2g_sbf_attention_fwd",
-             q.data_ptr() + e0 * D * fb, ptr(k), ptr(v), skip.data_ptr() + e0 * D * fb,
-             e_edge, e_row, edge_mode, S.data_ptr() - ta * D * fb, None, None, lg.trip_rowptr.data_ptr() + e0 * ib,
-             ptr(lg.trip_src), e1 - e0, T, heads, channels, D, out.data_ptr() + e0 * D * fb, ptr(alpha),
-             smax.data_ptr() + e0 * H * fb, sden.data_ptr() + e0 * H * fb,
-             *((rstats.data_ptr() + e0 * 2 * fb,) if rstats is not None else ()), st)
-    return out, alpha, smax, sden, rstats
-
-
 def sbf_attention(q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg: LineGraph, heads: int, channels: int,
                   edge_mode: int = EDGE_PER_TRIPLET, edge_row=None, return_attention=False, dropout=None):
     """Fused SBFTransformerConv message/softmax/aggregate/skip (see csrc/attention.hip).
@@ -1183,16 +1182,21 @@ def sbf_attention(q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg: LineGraph, heads: 
         edge_mode = EDGE_NONE
     if edge_row is not None:
         edge_row = _i32(edge_row)
-    sf = (_center_rows(lg, edge_mode, edge_row, heads * channels, channels)[0]
-          and _center_sf_ok(lg, _sbf_factors(lg, sbf, edge_mode, heads * channels, edge, edge_row), heads * channels))
-    if dropout is not None:  # (its one route is the fused center forward: _SBFAttention raises for another)
-        sf = True
-    if not torch.is_grad_enabled() and lg.T > INFER_TILE and q.shape[0] > 0 and not sf:  # (sf: no S at all)
-        out, alpha, smax, sden, rstats = _attention_fwd_tiled(q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode,
-                                                              edge_row, heads, channels, INFER_TILE, return_attention)
+    grad = torch.is_grad_enabled()
+    # (what _keeps answers inside the forward: autograd fills needs_input_grad from requires_grad alone)
+    keeps = grad and any(t is not None and t.requires_grad for t in (q, k, v, skip, edge, sbf, w_sbf, b_sbf))
+    route = _attention_route(lg, edge_mode, None if edge is None else edge.shape[0], edge_row, heads, channels,
+                             lg.sbf_factors is not None and lg.sbf_factors[0] is sbf, sbf.shape[1], keeps,
+                             return_attention, dropout is not None, grad)
+    if route.dropout_refusal is not None:
+        raise NotImplementedError("attention dropout is compiled for the center kernels only: "
+                                  + route.dropout_refusal)
+    if route.tiles is not None:  # (inference only: no autograd node)
+        out, alpha, smax, sden, rstats = _attention_forward(route, q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode,
+                                                            edge_row, heads, channels)[1]
     else:
         out, alpha, smax, sden, rstats = _apply(_SBFAttention, q, k, v, skip, edge, sbf, w_sbf, b_sbf, lg, edge_mode,
-                                                         edge_row, heads, channels, return_attention, dropout)
+                                                edge_row, heads, channels, route, dropout)
     if rstats is not None:  # for a graph LayerNorm fused into the consumer (ops.row_chain(ln=...))
         out._x2g_rowstats = rstats
     if not return_attention:
