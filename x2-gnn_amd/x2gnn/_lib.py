@@ -25,6 +25,8 @@ HEADER_PATH = os.environ.get("X2G_HEADER",
 STAGED_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_staged.h")
 # the multi-target entry points' header (the K-target readout heads, per-target metrics): a table of its own too
 MULTI_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_multi.h")
+# the conv combine pass' header (SBFTransformerConv's concat=False / beta=True): again a table of its own
+CONV_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_conv.h")
 
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int": ctypes.c_int,
             "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
@@ -64,10 +66,11 @@ def _split(item, decl):
     return m[1], m[2]
 
 
-def parse_header(text):
+def parse_header(text, known=()):
     """(SIGNATURES, RESTYPES, STRUCTS, CONSTS) of a header written like include/x2g.h: comments, integer
     ``#define``s, ``typedef struct { scalar or pointer fields } name;`` and function declarations.  Anything
-    else raises ValueError quoting the declaration."""
+    else raises ValueError quoting the declaration.  ``known``: struct names another header declared, which
+    this one may point to."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b[^\n]*", "", text, flags=re.S | re.M)
     consts = _Consts()
@@ -98,8 +101,8 @@ def parse_header(text):
         if not m:
             raise ValueError(f"x2g.h: cannot read the declaration: {decl}")
         args = [] if m[3].strip() == "void" else m[3].split(",")
-        signatures[m[2]] = [_ctype(_split(a, decl)[0], decl, structs) for a in args]
-        restypes[m[2]] = _ctype(m[1], decl, structs, ret=True)
+        signatures[m[2]] = [_ctype(_split(a, decl)[0], decl, (*structs, *known)) for a in args]
+        restypes[m[2]] = _ctype(m[1], decl, (*structs, *known), ret=True)
     return signatures, restypes, structs, consts
 
 
@@ -110,13 +113,14 @@ def _read_header():
         return f.read()
 
 
-def _read_functions(path):
+def _read_functions(path, known=()):
     """(signatures, restypes) of a header next to x2g.h, read like it; it declares functions only (no struct,
-    no constant: anything else raises).  Empty when the header is absent (an X2G_HEADER of an earlier tree)."""
+    no constant: anything else raises; ``known``: x2g.h's structs it may point to).  Empty when the header is
+    absent (an X2G_HEADER of an earlier tree)."""
     if not os.path.exists(path):
         return {}, {}
     with open(path) as f:
-        sig, res, structs, consts = parse_header(f.read())
+        sig, res, structs, consts = parse_header(f.read(), known)
     if structs or consts:
         raise ValueError(f"{os.path.basename(path)} declares more than functions: "
                          f"{sorted(structs) + sorted(consts)}")
@@ -129,6 +133,8 @@ SIGNATURES, RESTYPES, STRUCTS, CONSTS = parse_header(_read_header())
 STAGED_SIGNATURES, STAGED_RESTYPES = _read_functions(STAGED_HEADER_PATH)
 # and for the multi-target entry points (x2g_multi.h)
 MULTI_SIGNATURES, MULTI_RESTYPES = _read_functions(MULTI_HEADER_PATH)
+# and for the conv combine pass (x2g_conv.h; its deferred backward fills an x2g_slab_job of x2g.h)
+CONV_SIGNATURES, CONV_RESTYPES = _read_functions(CONV_HEADER_PATH, known=tuple(STRUCTS))
 
 _lib = None
 
@@ -144,7 +150,8 @@ def load():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = RESTYPES[name]
-        for sigs, res in ((STAGED_SIGNATURES, STAGED_RESTYPES), (MULTI_SIGNATURES, MULTI_RESTYPES)):
+        for sigs, res in ((STAGED_SIGNATURES, STAGED_RESTYPES), (MULTI_SIGNATURES, MULTI_RESTYPES),
+                          (CONV_SIGNATURES, CONV_RESTYPES)):
             for name, args in sigs.items():
                 # (a library built from an earlier tree, X2G_LIB, has none of them: calling one then raises)
                 fn = getattr(lib, name, None)

@@ -92,13 +92,14 @@ class _ReadoutFamily:
 
 class _Trunk(nn.Module):
     def _build(self, conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads, readout, attn_dropout=0.0,
-               dropout_seed=0):
+               dropout_seed=0, beta=False):
         self.in_channels = in_channels
         self.rbf_dim = rbf_dim
         self.edgenn = Sequential(Linear(emb_size, emb_size), SiLU(), Linear(emb_size, emb_size))
         self.convs = ModuleList([
             SBFTransformerConv(in_channels=in_channels, out_channels=int(in_channels / heads), heads=heads,
-                               sbf_dim=sbf_dim * rbf_dim, rbf_dim=rbf_dim, dropout=attn_dropout, edge_dim=emb_size)
+                               sbf_dim=sbf_dim * rbf_dim, rbf_dim=rbf_dim, dropout=attn_dropout, edge_dim=emb_size,
+                               beta=beta)
             for _ in range(conv_layers)])
         self.readouts = ModuleList([readout() for _ in range(conv_layers + 1)])
         self.bf_skip = ModuleList([ResidualLayer(in_channels) for _ in range(conv_layers)])
@@ -301,12 +302,12 @@ class SBFTransformer(_Trunk, _AtomReadouts):
     readouts end in Linear(D, K) and ``forward`` returns [B, K] (K = 1: [B], the reference's tensor)."""
 
     def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8, attn_dropout=0.0,
-                 dropout_seed=0, num_target=1):
+                 dropout_seed=0, num_target=1, beta: bool = False):
         super().__init__()
         self.num_target = num_target = _check_targets(num_target)
         self._build(conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads,
                     lambda: AtomWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=num_target),
-                    attn_dropout=attn_dropout, dropout_seed=dropout_seed)
+                    attn_dropout=attn_dropout, dropout_seed=dropout_seed, beta=beta)
 
     def forward(self, data, edge_index_0, atom_batch):
         plan = _plan_of(data, edge_index_0, atom_batch)
@@ -320,13 +321,13 @@ class SBFTransformerGlobal(_Trunk, _MolReadouts):
     SBFTransformer's."""
 
     def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8, pool_option="mean",
-                 attn_dropout=0.0, dropout_seed=0, num_target=1):
+                 attn_dropout=0.0, dropout_seed=0, num_target=1, beta: bool = False):
         super().__init__()
         self.num_target = num_target = _check_targets(num_target)
         self._build(conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads,
                     lambda: MolWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=num_target,
                                     pool_option=pool_option),
-                    attn_dropout=attn_dropout, dropout_seed=dropout_seed)
+                    attn_dropout=attn_dropout, dropout_seed=dropout_seed, beta=beta)
 
     def forward(self, data, edge_index_0, atom_batch):
         plan = _plan_of(data, edge_index_0, atom_batch)
@@ -342,7 +343,7 @@ class SBFTransformerMulti(_Trunk, _AtomReadouts, _MolReadouts):
     family then has no modules, and the model is SBFTransformer / SBFTransformerGlobal with a 2-d result."""
 
     def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, heads=8, atom_targets=6,
-                 mol_targets=6, pool_option="mean", attn_dropout=0.0, dropout_seed=0):
+                 mol_targets=6, pool_option="mean", attn_dropout=0.0, dropout_seed=0, beta: bool = False):
         super().__init__()
         self.atom_targets, self.mol_targets = _check_targets(atom_targets, 0), _check_targets(mol_targets, 0)
         self.num_target = self.atom_targets + self.mol_targets
@@ -350,7 +351,7 @@ class SBFTransformerMulti(_Trunk, _AtomReadouts, _MolReadouts):
             raise ValueError("atom_targets + mol_targets must be at least 1")
         self._build(conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads,
                     lambda: AtomWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=max(self.atom_targets, 1)),
-                    attn_dropout=attn_dropout, dropout_seed=dropout_seed)
+                    attn_dropout=attn_dropout, dropout_seed=dropout_seed, beta=beta)
         if not self.atom_targets:
             self.readouts = ModuleList()
         self.mol_readouts = ModuleList([MolWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=self.mol_targets,

@@ -2272,6 +2272,89 @@ def rbf_pool(x, rbf, weight, bias, owner, rowptr, n_seg: int):
     return _RbfPoolFn.apply(x, rbf, weight, bias, _i32(owner), _i32(rowptr), int(n_seg))
 
 
+def conv_combine_supported(heads, channels):
+    """Shapes the combine pass is compiled for (csrc/conv_combine.hip)."""
+    return heads >= 1 and channels in (4, 8, 16, 32) and heads * channels in (32, 64, 128, 256)
+
+
+class _ConvCombineFn(torch.autograd.Function):
+    """SBFTransformerConv's concat=False / beta=True (reference sbftransformer_conv.py:115-127) after the
+    attention: m = attn or its mean over heads, y = beta x_r + (1 - beta) m with beta = sigmoid(w_beta .
+    [m, x_r, m - x_r]), or m + x_r (include/x2g_conv.h).  Keeps attn, x_r and beta [rows] for the backward."""
+
+    @staticmethod
+    def forward(ctx, attn, x_r, w_beta, heads, channels, concat, want_stats):
+        a = _f32(attn)
+        x = None if x_r is None else _f32(x_r)
+        w = None if w_beta is None else _f32(w_beta).reshape(-1)
+        rows = a.shape[0]
+        f32 = dict(dtype=torch.float32, device=a.device)
+        y = torch.empty(rows, heads * channels if concat else channels, **f32)
+        keeps = _keeps(ctx)
+        beta = torch.empty(rows, **f32) if w is not None and keeps else None
+        stats = torch.empty(rows, 2, **f32) if want_stats else None
+        call("x2g_conv_combine_fwd", ptr(a), ptr(x), ptr(w), rows, heads, channels, int(concat), ptr(y), ptr(beta),
+             ptr(stats), stream_ptr())
+        if keeps:
+            ctx.save_for_backward(a, x, w, beta)
+        ctx.cfg, ctx.w_param = (heads, channels, int(concat)), w_beta
+        if stats is not None:
+            ctx.mark_non_differentiable(stats)
+        return y, stats
+
+    @staticmethod
+    def backward(ctx, dy, _dstats=None):
+        a, x, w, beta = ctx.saved_tensors
+        heads, channels, concat = ctx.cfg
+        dy = _f32(dy)
+        rows, dev = a.shape[0], a.device
+        need_a, need_x = ctx.needs_input_grad[0], x is not None and ctx.needs_input_grad[1]
+        lib = _lib.load()
+        if w is None:  # no gate: d_xr = dy, d_attn = dy (/ H, broadcast over the heads)
+            d_attn = None
+            if need_a and concat:
+                d_attn = dy
+            elif need_a:
+                d_attn = torch.empty_like(a)
+                call("x2g_conv_combine_bwd", ptr(dy), None, None, None, None, rows, heads, channels, concat,
+                     ptr(d_attn), None, None, 0, None, None, 0, stream_ptr())
+            return d_attn, (dy if need_x else None), None, None, None, None, None
+        d_attn = torch.empty_like(a) if need_a else None
+        d_xr = torch.empty_like(x) if need_x else None
+        dest = _WGradDest([ctx.w_param], dev, shapes=[tuple(ctx.w_param.shape)])
+        (dw,) = dest.bufs
+        ws_bytes = int(lib.x2g_conv_combine_bwd_workspace(rows, heads, channels, concat))
+        flags = dest.flags(rows)
+        job = SlabJob()
+        call("x2g_conv_combine_bwd", ptr(dy), ptr(a), ptr(x), ptr(w), ptr(beta), rows, heads, channels, concat,
+             ptr(d_attn), ptr(d_xr), ptr(dw), flags,
+             ctypes.cast(ctypes.pointer(job), ctypes.c_void_p) if dest.deferral else None,
+             ptr(dest.workspace(ws_bytes)), ws_bytes, stream_ptr())
+        if dest.deferral:  # (the deferral keeps the workspace until its one batched sum ran)
+            dest.queue(jobs=[job])
+        return d_attn, d_xr, dest.grads()[0], None, None, None, None
+
+
+def conv_combine(attn, x_r, w_beta, heads: int, channels: int, concat: bool = True):
+    """The conv's output from the attention's ``attn`` [E, heads * channels] (computed with a zero skip row),
+    ``x_r = lin_skip(x)`` [E, Dout] or None (root_weight=False) and ``w_beta`` = lin_beta.weight [1, 3 Dout] or
+    None: see _ConvCombineFn.  Dout = heads * channels (concat) or channels (mean over heads).  At Dout = 128
+    the output carries its per-row (mean, M2) as ``_x2g_rowstats``, like the attention's own output, so the graph
+    LayerNorm that follows stays fused into the next row chain."""
+    _need_cuda(attn, x_r, w_beta)
+    heads, channels = int(heads), int(channels)
+    if not conv_combine_supported(heads, channels):
+        raise NotImplementedError(f"conv combine: heads * channels in 32 / 64 / 128 / 256 and channels in 4 / 8 / 16 "
+                                  f"/ 32 are compiled, not heads = {heads}, channels = {channels}")
+    if w_beta is not None and x_r is None:
+        raise ValueError("conv combine: the gate needs x_r (beta is off without root_weight)")
+    dout = heads * channels if concat else channels
+    y, stats = _apply(_ConvCombineFn, attn, x_r, w_beta, heads, channels, bool(concat), _LN_FUSE and dout == 128)
+    if stats is not None:
+        y._x2g_rowstats = stats
+    return y
+
+
 def conv_projections(x, rbf, wr, wq, bq, wk, bk, wv, bv, ws, bs):
     if not x.is_cuda:
         raise RuntimeError("x2gnn device ops need GPU tensors (no CPU fallback by design)")

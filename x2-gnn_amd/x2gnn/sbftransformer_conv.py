@@ -9,6 +9,15 @@ reference (sbftransformer_conv.py:16-166, a PyG ``MessagePassing`` with aggr='ad
         m_t     = (v[src] + e_t) * lin_sbf(sbf_t) * alpha_t
     out[dst] = sum_t m_t  (+ lin_skip(x) with root_weight)
 
+``concat=False`` averages the heads (out is then ``out_channels`` wide, as is lin_skip) and ``beta=True`` (with
+root_weight) replaces the skip add by the gated residual of PyG's TransformerConv (reference :115-127):
+
+    x_r = lin_skip(x);  beta = sigmoid(lin_beta(cat([out, x_r, out - x_r], -1)));  out = beta x_r + (1 - beta) out
+
+Both run as one row pass after the attention (``ops.conv_combine``, csrc/conv_combine.hip): the attention
+kernels get a zero skip row, as root_weight=False gives them.  With the defaults (concat=True, beta=False, X2-GNN's)
+the module makes exactly the calls it made before these options existed.
+
 The five projections (lin_rbf gate, q/k/v/skip) run as one fused f32-MFMA kernel each way
 (``ops.conv_projections``; the generic dense kernels for widths outside the compiled set).
 ``lin_sbf(sbf)`` is materialised once per layer as S [T, H*C] (``x2g_sbf_project``), and
@@ -52,13 +61,11 @@ class SBFTransformerConv(nn.Module):
                  dropout: float = 0.0, edge_dim: Optional[int] = None, bias: bool = True,
                  root_weight: bool = True, **kwargs):
         super().__init__()
-        if not concat or (beta and root_weight):
-            raise NotImplementedError("compiled configuration: concat=True, beta=False (X2-GNN's)")
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"dropout probability has to be in [0, 1), but got {dropout}")
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
         self.sbf_dim, self.rbf_dim = sbf_dim, rbf_dim
-        self.beta, self.root_weight, self.concat = False, root_weight, concat
+        self.beta, self.root_weight, self.concat = beta and root_weight, root_weight, concat
         self.dropout, self.edge_dim = dropout, edge_dim
         cin = (in_channels, in_channels) if isinstance(in_channels, int) else tuple(in_channels)
         hc = heads * out_channels
@@ -66,8 +73,9 @@ class SBFTransformerConv(nn.Module):
         self.lin_query = Linear(cin[1], hc)
         self.lin_value = Linear(cin[0], hc)
         self.lin_edge = Linear(edge_dim, hc, bias=False) if edge_dim is not None else None
-        self.lin_skip = Linear(cin[1], hc, bias=bias)
-        self.lin_beta = None
+        dout = hc if concat else out_channels
+        self.lin_skip = Linear(cin[1], dout, bias=bias)
+        self.lin_beta = Linear(3 * dout, 1, bias=False) if self.beta else None
         self.lin_sbf = Linear(sbf_dim, hc, bias=True)
         self.lin_rbf = Linear(rbf_dim, cin[0], bias=False)
         self._alpha = None
@@ -86,7 +94,10 @@ class SBFTransformerConv(nn.Module):
                 line_graph: Optional[ops.LineGraph] = None, edge_row=None, edge_proj=None,
                 assume_sorted: bool = False, dropout_key=None, dropout_salt: int = 0):
         H, C = self.heads, self.out_channels
-        if x.is_cuda and self.root_weight and x.dim() == 2:
+        # concat=False or beta=True (reference :115-127): the attention runs with a zero skip row and
+        # ops.conv_combine does the mean over heads, the gate and the skip afterwards
+        combine = self.beta or not self.concat
+        if x.is_cuda and self.root_weight and self.concat and x.dim() == 2:
             # one autograd node for the five projections: the backward chains the data
             # gradients into one buffer per input instead of autograd adds
             q, k, v, skip = ops.conv_projections(
@@ -97,7 +108,10 @@ class SBFTransformerConv(nn.Module):
             q = self.lin_query(x)
             k = self.lin_key(x_src)
             v = self.lin_value(x_src)
-            skip = self.lin_skip(x) if self.root_weight else torch.zeros_like(q)
+            skip = self.lin_skip(x) if self.root_weight else None
+        x_r = skip if combine else None
+        if combine or skip is None:
+            skip = torch.zeros_like(q)
         perm = None
         if line_graph is None:
             dst = edge_index[1]
@@ -128,6 +142,10 @@ class SBFTransformerConv(nn.Module):
             dropout = (float(self.dropout), dropout_key, dropout_salt)
         res = ops.sbf_attention(q, k, v, skip, e, sbf, self.lin_sbf.weight, self.lin_sbf.bias, line_graph, H, C,
                                 edge_mode=mode, edge_row=edge_row, return_attention=want, dropout=dropout)
+        if combine:
+            out = ops.conv_combine(res[0] if want else res, x_r, self.lin_beta.weight if self.beta else None, H, C,
+                                   self.concat)
+            res = (out, res[1]) if want else out
         if want:
             out, alpha = res
             if perm is not None:  # back to the caller's triplet order

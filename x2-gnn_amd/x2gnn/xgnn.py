@@ -107,21 +107,23 @@ class _XGNNBase(nn.Module):
 
 class xgnn_poly(_XGNNBase):
     def __init__(self, conv_layers=4, sbf_dim=7, rbf_dim=16, in_channels=256, heads=16, embedding_size=128,
-                 device="cpu", attn_dropout=0.0, dropout_seed=0, num_target=1):
+                 device="cpu", attn_dropout=0.0, dropout_seed=0, num_target=1, conv_beta: bool = False):
         super().__init__()
         trunk = SBFTransformer(conv_layers=conv_layers, emb_size=embedding_size, sbf_dim=sbf_dim, rbf_dim=rbf_dim,
                                in_channels=in_channels, heads=heads, attn_dropout=attn_dropout,
-                               dropout_seed=dropout_seed, num_target=num_target)
+                               dropout_seed=dropout_seed, num_target=num_target, beta=conv_beta)
         self._build(trunk, sbf_dim, rbf_dim, in_channels, embedding_size, device)
 
 
 class xgnn_poly_global(_XGNNBase):
     def __init__(self, conv_layers=4, sbf_dim=7, rbf_dim=16, in_channels=256, heads=16, embedding_size=128,
-                 device="cpu", pool_option="mean", attn_dropout=0.0, dropout_seed=0, num_target=1):
+                 device="cpu", pool_option="mean", attn_dropout=0.0, dropout_seed=0, num_target=1,
+                 conv_beta: bool = False):
         super().__init__()
         trunk = SBFTransformerGlobal(conv_layers=conv_layers, emb_size=embedding_size, sbf_dim=sbf_dim,
                                      rbf_dim=rbf_dim, in_channels=in_channels, heads=heads, pool_option=pool_option,
-                                     attn_dropout=attn_dropout, dropout_seed=dropout_seed, num_target=num_target)
+                                     attn_dropout=attn_dropout, dropout_seed=dropout_seed, num_target=num_target,
+                                     beta=conv_beta)
         self._build(trunk, sbf_dim, rbf_dim, in_channels, embedding_size, device)
 
 
@@ -131,10 +133,11 @@ class xgnn_poly_multi(_XGNNBase):
     ones, QM9's order for its 12 properties at (6, 6)."""
 
     def __init__(self, conv_layers=4, sbf_dim=7, rbf_dim=16, in_channels=256, heads=16, embedding_size=128,
-                 device="cpu", atom_targets=6, mol_targets=6, pool_option="mean", attn_dropout=0.0, dropout_seed=0):
+                 device="cpu", atom_targets=6, mol_targets=6, pool_option="mean", attn_dropout=0.0, dropout_seed=0,
+                 conv_beta: bool = False):
         super().__init__()
         trunk = SBFTransformerMulti(conv_layers=conv_layers, emb_size=embedding_size, sbf_dim=sbf_dim,
                                     rbf_dim=rbf_dim, in_channels=in_channels, heads=heads, atom_targets=atom_targets,
                                     mol_targets=mol_targets, pool_option=pool_option, attn_dropout=attn_dropout,
-                                    dropout_seed=dropout_seed)
+                                    dropout_seed=dropout_seed, beta=conv_beta)
         self._build(trunk, sbf_dim, rbf_dim, in_channels, embedding_size, device)
