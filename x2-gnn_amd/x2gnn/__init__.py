@@ -8,15 +8,15 @@ Device side: ``libx2g.so`` (hand-written gfx950 HIP kernels behind the C ABI in
 from .data import Batch, Data, collate, molecule_to_data
 from .device_dataset import DeviceDataset
 from .layers import AtomWise, EmbeddingBlock, F_B_2D, MolWise, RadialBasis, ResidualLayer, poly_envelop
-from .model import LayerNorm, SBFTransformer, SBFTransformerGlobal, SBFTransformerMulti
+from .model import LayerNorm, SBFTransformer, SBFTransformerGlobal, SBFTransformerMulti, SBFTransformerV2
 from .plan import GraphPlan
 from .sbftransformer_conv import SBFTransformerConv
 from .train import Evaluator, Inference, Trainer
-from .xgnn import xgnn_poly, xgnn_poly_global, xgnn_poly_multi
+from .xgnn import xgnn_poly, xgnn_poly_global, xgnn_poly_multi, xgnn_poly_v2
 
 __all__ = [
     "AtomWise", "Batch", "Data", "DeviceDataset", "EmbeddingBlock", "Evaluator", "F_B_2D", "GraphPlan", "Inference",
     "LayerNorm", "MolWise", "RadialBasis", "ResidualLayer", "SBFTransformer", "SBFTransformerConv",
-    "SBFTransformerGlobal", "SBFTransformerMulti", "Trainer", "collate", "molecule_to_data", "poly_envelop",
-    "xgnn_poly", "xgnn_poly_global", "xgnn_poly_multi",
+    "SBFTransformerGlobal", "SBFTransformerMulti", "SBFTransformerV2", "Trainer", "collate", "molecule_to_data",
+    "poly_envelop", "xgnn_poly", "xgnn_poly_global", "xgnn_poly_multi", "xgnn_poly_v2",
 ]

@@ -27,6 +27,8 @@ STAGED_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_staged.h")
 MULTI_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_multi.h")
 # the conv combine pass' header (SBFTransformerConv's concat=False / beta=True): again a table of its own
 CONV_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_conv.h")
+# the atom-context chain's header (SBFTransformerV2's per-layer edge term): a table of its own as well
+ATOMCTX_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_atomctx.h")
 
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int": ctypes.c_int,
             "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
@@ -135,6 +137,8 @@ STAGED_SIGNATURES, STAGED_RESTYPES = _read_functions(STAGED_HEADER_PATH)
 MULTI_SIGNATURES, MULTI_RESTYPES = _read_functions(MULTI_HEADER_PATH)
 # and for the conv combine pass (x2g_conv.h; its deferred backward fills an x2g_slab_job of x2g.h)
 CONV_SIGNATURES, CONV_RESTYPES = _read_functions(CONV_HEADER_PATH, known=tuple(STRUCTS))
+# and for the atom-context chain (x2g_atomctx.h)
+ATOMCTX_SIGNATURES, ATOMCTX_RESTYPES = _read_functions(ATOMCTX_HEADER_PATH)
 
 _lib = None
 
@@ -151,7 +155,7 @@ def load():
             fn.argtypes = args
             fn.restype = RESTYPES[name]
         for sigs, res in ((STAGED_SIGNATURES, STAGED_RESTYPES), (MULTI_SIGNATURES, MULTI_RESTYPES),
-                          (CONV_SIGNATURES, CONV_RESTYPES)):
+                          (CONV_SIGNATURES, CONV_RESTYPES), (ATOMCTX_SIGNATURES, ATOMCTX_RESTYPES)):
             for name, args in sigs.items():
                 # (a library built from an earlier tree, X2G_LIB, has none of them: calling one then raises)
                 fn = getattr(lib, name, None)

@@ -12,6 +12,10 @@ reference repeats per triplet: ``data._x2g_plan`` (a prebuilt :class:`GraphPlan`
 ``data.edge_attr_row`` — when present, ``edge_attr`` is a per-element table [10, D] and line
 node e uses row ``edge_attr_row[e]``, so ``edgenn`` and every ``lin_edge`` run on 10 rows
 instead of T (the reference's edge_attr rows are copies of those rows, xgnn.py:57-58).
+
+``SBFTransformerV2`` (reference model.py:100-150) is the same trunk with the edge term recomputed in every layer
+from the line-node features pooled per atom; with ``data.edge_atom_row`` that chain runs on the N atom rows
+(``ops.atom_context``) and the attention reads one table row per center atom.
 """
 from __future__ import annotations
 
@@ -90,6 +94,14 @@ class _ReadoutFamily:
         return results
 
 
+def glorot_ortho_(tensor, scale=2.0):
+    """The reference's ``Glorot_Ortho_`` (initializer.py:29-35): orthogonal, rescaled to the Glorot variance."""
+    nn.init.orthogonal_(tensor)
+    with torch.no_grad():
+        tensor.mul_(torch.sqrt(scale / ((tensor.shape[0] + tensor.shape[1]) * tensor.var())))
+    return tensor
+
+
 class _Trunk(nn.Module):
     def _build(self, conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads, readout, attn_dropout=0.0,
                dropout_seed=0, beta=False):
@@ -140,11 +152,7 @@ class _Trunk(nn.Module):
         single-family trunks, two for SBFTransformerMulti); returns their results in that order.  A family with
         ``pool_out = (seg_rowptr, S)``: the batched readout heads may sum the per-atom results per molecule
         themselves (the result then carries ``_x2g_pooled``)."""
-        per_dst = "edge_attr_row" in data._store
-        edge_proj = data._store.get("_x2g_edge_proj") if per_dst else None
-        # lin_edge tables precomputed by the featurisation's table chain, or edgenn here
-        edge_attr = run_mlp(self.edgenn, data.edge_attr) if edge_proj is None else None
-        edge_row = data.edge_attr_row if per_dst else None
+        edge_term = self._edge_terms(data, plan)
         out = data.x
         # The readouts (reference model.py:41,50) hang off the layer chain; results accumulate in
         # layer order (deterministic).  (Run on a second stream, overlapping the next layer, they
@@ -174,9 +182,9 @@ class _Trunk(nn.Module):
         # attention is still in the MALL when the attention reads it; projected 3 layers early it is not)
         for i in range(self.conv_layers):
             res0 = out
+            edge_attr, edge_row, edge_proj = edge_term(i, out)
             out = self.convs[i](sbf=sbf, rbf=data.node_rbf, x=out, edge_index=data._store.get("edge_index"),
-                                edge_attr=edge_attr, line_graph=plan.lg, edge_row=edge_row,
-                                edge_proj=edge_proj[i] if edge_proj is not None else None,
+                                edge_attr=edge_attr, line_graph=plan.lg, edge_row=edge_row, edge_proj=edge_proj,
                                 dropout_key=drop_key, dropout_salt=i)
             stats = getattr(out, "_x2g_rowstats", None)
             if stats is not None and self._ln_fusable(out, i):
@@ -189,6 +197,16 @@ class _Trunk(nn.Module):
                 out._x2g_fanin = ops.FanIn()
             readout(i + 1, out)
         return [f.finish() for f in families]
+
+    def _edge_terms(self, data, plan):
+        """The one hook of a trunk's layers: a function (layer i, its input x) -> the conv's (edge_attr, edge_row,
+        edge_proj).  Here the edge term is a constant of the forward: the lin_edge tables precomputed by the
+        featurisation's table chain (``_x2g_edge_proj``), or edgenn applied once."""
+        per_dst = "edge_attr_row" in data._store
+        edge_proj = data._store.get("_x2g_edge_proj") if per_dst else None
+        edge_attr = run_mlp(self.edgenn, data.edge_attr) if edge_proj is None else None
+        edge_row = data.edge_attr_row if per_dst else None
+        return lambda i, x: (edge_attr, edge_row, edge_proj[i] if edge_proj is not None else None)
 
     def _pool_batch(self, xs, rbf, edge_index_0, plan, readouts=None):
         """Every readout's edge -> atom pool (readout.py:39-41 / 66-67) in one launch each way, or
@@ -371,3 +389,71 @@ class SBFTransformerMulti(_Trunk, _AtomReadouts, _MolReadouts):
         if len(res) == 1:
             return res[0]
         return torch.cat([res[1], res[0]], dim=1)
+
+
+class SBFTransformerV2(_Trunk, _AtomReadouts):
+    """The trunk whose edge term is recomputed per layer from the current line-node features (reference
+    model.py:100-150): ``atoms_rep = scatter_add(x, edge_index_0)``, then per layer
+    ``edge_attr = edgenn[i](atoms_rep[data.edge_attr])`` with ``data.edge_attr`` an integer [T] atom index per triplet,
+    then the conv's lin_edge; the energies are divided by ``conv_layers``.  Same constructor (``K`` is unused, as in
+    the reference), module tree and ``state_dict`` keys.
+
+    When ``data`` carries ``edge_atom_row`` (int [E]: the plan's ``edge_dst``, the target atom of each line node,
+    which is what ``data.edge_attr`` holds for every triplet into it: xgnn_poly_v2 sets both) the chain runs on the N
+    atom rows (``ops.atom_context``) and the attention reads one table row per center atom.  Otherwise the literal
+    form runs on T rows: correct for any index, and slow."""
+
+    def __init__(self, conv_layers, emb_size, sbf_dim, rbf_dim=16, in_channels=128, K=2, heads=8):
+        super().__init__()
+        if emb_size != in_channels:
+            # (the reference fails at the first forward: lin_edge is emb_size wide, edgenn in_channels wide)
+            raise ValueError(f"SBFTransformerV2: emb_size ({emb_size}) must equal in_channels ({in_channels}): "
+                             "edgenn's output is the input of every conv's lin_edge")
+        self.num_target = 1
+        self._build(conv_layers, emb_size, sbf_dim, rbf_dim, in_channels, heads,
+                    lambda: AtomWise(in_channels=in_channels, rbf_dim=rbf_dim, num_target=1))
+        self.edgenn = ModuleList([Sequential(Linear(in_channels, in_channels), SiLU(), Linear(in_channels, in_channels))
+                                  for _ in range(conv_layers)])
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        """The reference's (model.py:118-130)."""
+        for layer in self.dense_bf_skip:
+            glorot_ortho_(layer.weight)
+            nn.init.zeros_(layer.bias)
+        for conv in self.convs:
+            glorot_ortho_(conv.lin_sbf.weight)
+            glorot_ortho_(conv.lin_rbf.weight)
+            nn.init.zeros_(conv.lin_sbf.bias)
+        for edge_nn in self.edgenn:
+            for lin in (edge_nn[0], edge_nn[2]):
+                glorot_ortho_(lin.weight)
+                nn.init.zeros_(lin.bias)
+
+    def edge_table_stages(self):
+        return None  # (no per-element table: the edge term depends on the layer's input)
+
+    def _edge_terms(self, data, plan):
+        atom_row = data._store.get("edge_atom_row")
+
+        def term(i, x):
+            nn_i, conv = self.edgenn[i], self.convs[i]
+            if atom_row is not None:  # one table row per atom, read per center atom
+                tab = ops.atom_context(x, plan.atom_rowptr, plan.lg.edge_src, nn_i[0], nn_i[2], conv.lin_edge)
+                return None, atom_row, tab
+            atoms_rep = ops.segment_sum(x, plan.atom_rowptr, plan.num_atoms)
+            return run_mlp(nn_i, atoms_rep.index_select(0, data.edge_attr)), None, None
+
+        return term
+
+    def _fan_in_ok(self, data, x):
+        """The layer input has one more consumer, the atom context: fan-aware where its kernels run (the dx
+        accumulate flag); the composition and the literal form leave the fan-in to autograd."""
+        if not super()._fan_in_ok(data, x) or "edge_atom_row" not in data._store or not ops._ATOM_CTX:
+            return False
+        return all(ops.atom_context_supported(x, [e[0], e[2], c.lin_edge]) for e, c in zip(self.edgenn, self.convs))
+
+    def forward(self, data, edge_index_0, atom_batch):
+        plan = _plan_of(data, edge_index_0, atom_batch)
+        (per_atom,) = self._layers(data, plan, [self._atom_family(data, edge_index_0, plan)])
+        return self._atom_pooled(per_atom, plan).view(-1) / self.conv_layers

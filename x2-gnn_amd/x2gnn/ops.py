@@ -131,6 +131,11 @@ class LineGraph:
         # dst_type[e] = Z of e's destination atom = the edge row of every triplet into e, and
         # src_type[s] = Z of s's source atom = the same row for every triplet out of s
         self.dst_type = self.src_type = None
+        # per-line-node atom rows of a per-atom edge table (SBFTransformerV2; GraphPlan sets them to the line
+        # graph's own edge_dst / edge_src): dst_atom[e] = e's destination atom = the table row of every triplet
+        # into e, src_atom[s] = s's source atom = the same row for every triplet out of s
+        self.dst_atom = self.src_atom = None
+        self._atom_pack_info = None  # pack_info with the atom itself as its edge-table row (atom_pack_info)
         # degree bound of the center atoms (host metadata; set by GraphPlan, None = unknown) and each atom's
         # element row (int32 [N]: the key of the center-atom edge-term gradient)
         self.max_degree = None
@@ -169,6 +174,16 @@ class LineGraph:
         ws_bytes = int(_lib.load().x2g_vertex_to_edge_workspace(lg.E, 0))
         lg._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=lg.trip_src.device)
         return lg
+
+    def atom_pack_info(self):
+        """``pack_info`` for a per-atom edge table: its fourth column, the edge-table row of the atom's first
+        out-edge (the element row collate and x2g_center_schedule fill in), is the atom's own index (column 0).
+        None without a ``pack_info``."""
+        if self._atom_pack_info is None and self.pack_info is not None:
+            info = self.pack_info.view(-1, 4).clone()
+            info[:, 3] = info[:, 0]
+            self._atom_pack_info = info.view(-1)
+        return self._atom_pack_info
 
     def src_csr(self):
         """(src_rowptr [E+1], src_perm [T]): the triplets grouped by source line node; ``src_dst``
@@ -479,15 +494,24 @@ def _center_bwd_ok(lg, heads, s_rows=False):
 def _center_rows(lg, edge_mode, edge_row, D, channels):
     """(ok, src_row): whether the center-atom forward applies to this call, and the per-source edge-table
     row it reads for EDGE_PER_DST (the center atom's element: lg.src_type, valid when the caller's
-    per-destination rows are the line graph's own dst_type)."""
+    per-destination rows are the line graph's own dst_type; the center atom itself, lg.src_atom, for a per-atom
+    table whose per-destination rows are lg.dst_atom)."""
     if (not _CENTER or lg.edge_rev is None or lg.max_degree is None
             or lg.max_degree > CENTER_MAX_DEGREE or D != 128 or channels % 4 or edge_mode == EDGE_PER_TRIPLET):
         return False, None
     if edge_mode == EDGE_PER_DST:
+        if _atom_table(lg, edge_row):
+            return True, lg.src_atom
         if edge_row is None or lg.src_type is None or edge_row is not lg.dst_type:
             return False, None
         return True, lg.src_type
     return True, None
+
+
+def _atom_table(lg, edge_row):
+    """Whether ``edge_row`` addresses a per-atom edge table: the line graph's own (dst_atom, src_atom) pair."""
+    return (edge_row is not None and getattr(lg, "src_atom", None) is not None
+            and edge_row is getattr(lg, "dst_atom", None))
 
 
 class _Route(NamedTuple):
@@ -507,6 +531,7 @@ class _Route(NamedTuple):
     rstats: bool  # ... the per-row (mean, M2) of the output, for a graph LayerNorm fused into the next row chain
     reads_sbf: bool  # the sbf rows themselves are read (materialize_sbf), not only their factors
     dropout_refusal: Optional[str]  # with dropout: None when this route has the staged dropout entries, else why not
+    atom_table: bool = False  # the edge table has one row per atom (lg.dst_atom / lg.src_atom), not per element
 
 
 def _attention_route(lg, edge_mode, edge_rows, edge_row, heads, channels, own_sbf, sbf_dim, keeps, keep_alpha,
@@ -525,13 +550,22 @@ def _attention_route(lg, edge_mode, edge_rows, edge_row, heads, channels, own_sb
     which recomputes them from rows it stages (the center forwards skip the store otherwise: 223 MB per layer
     in config 5's inference, 12 MB written and read back per layer in config 2's training)."""
     D = heads * channels
+    center, src_row = _center_rows(lg, edge_mode, edge_row, D, channels)
+    # a per-atom table: more than 16 rows, which only the fold passes refuse (the folded source pass stages the
+    # per-destination edge table in LDS), so it has the factors where the center kernels run both ways (the S-row
+    # backward's bound is the tighter of the two: asked once, either center backward may then follow), and else
+    # none: the plain two-pass backward
+    atom_table = edge_mode == EDGE_PER_DST and _atom_table(lg, edge_row)
+    wide = edge_mode == EDGE_PER_DST and (edge_row is None or edge_rows is None or edge_rows > 16)
+    if wide and atom_table and center and (not keeps or _center_bwd_ok(lg, heads, s_rows=True)):
+        wide = False
     factors = None
     if (own_sbf and edge_mode != EDGE_PER_TRIPLET and D in (32, 64, 128) and sbf_dim == FOLD_BASIS[0] * FOLD_BASIS[1]
-            # (the folded source pass stages the per-destination edge table in LDS)
-            and not (edge_mode == EDGE_PER_DST and (edge_row is None or edge_rows is None or edge_rows > 16))):
+            and not wide):
         factors = lg.sbf_factors[1], lg.sbf_factors[2]
-    center, src_row = _center_rows(lg, edge_mode, edge_row, D, channels)
     split = _center_sf_split(lg, factors, D) if center else None
+    if split is not None and atom_table and split[2] is not None:
+        split = (split[0], split[1], lg.atom_pack_info(), split[3])  # (the atom as its own edge-table row)
     fused = split is not None
     backward = None
     if keeps and factors is None:
@@ -551,7 +585,7 @@ def _attention_route(lg, edge_mode, edge_rows, edge_row, heads, channels, own_sb
     return _Route(factors, src_row, "fused" if fused else "center" if center else "dst", *(split or (None,) * 4),
                   tiles, backward, alpha=keep_alpha or not center or (keeps and backward != "center_p"),
                   sproj=not fused or backward in ("center_s", "dst_fold"), sbf_p=backward == "center_p",
-                  rstats=_LN_FUSE and D == 128, reads_sbf=not fused, dropout_refusal=refusal)
+                  rstats=_LN_FUSE and D == 128, reads_sbf=not fused, dropout_refusal=refusal, atom_table=atom_table)
 
 
 def _dropout_refusal(lg, edge_mode, D, channels, center, factors, fused, no_p_backward):
@@ -571,7 +605,8 @@ def _dropout_refusal(lg, edge_mode, D, channels, center, factors, fused, no_p_ba
         return (f"a degree above {DROPOUT_TILED_MAX_DEGREE} ({lg.max_degree}): the source-tiled forward has no "
                 "dropout instance for it")
     if not center:
-        return "edge_row is not the line graph's own destination elements (dst_type)"
+        return ("edge_row is not the line graph's own destination elements (dst_type) or, for a per-atom table, "
+                "destination atoms (dst_atom)")
     if factors is None or factors[1] is None:
         return "the sbf factors are absent (sbf is not the line graph's own radial x angular product)"
     if not fused:
@@ -702,6 +737,10 @@ class _SBFAttention(torch.autograd.Function):
                  ptr(dk), ptr(dv), st)
             if not ctx.needs_input_grad[4]:
                 d_edge = None
+            elif mode == EDGE_PER_DST and ctx.route.atom_table:
+                # a per-atom table: the destinations' gradients summed by target atom, each segment in row
+                # order (x2g_segment_reduce_perm)
+                d_edge = scatter_add(d_edge, ctx.edge_row, ctx.edge_shape[0])
             elif mode == EDGE_PER_DST and ctx.edge_row is not None:
                 # rows of the edge table are shared by many destinations: sum d_edge per table row
                 d_edge = keyed_row_sum(d_edge, ctx.edge_row, ctx.edge_shape[0])
@@ -723,7 +762,7 @@ class _SBFAttention(torch.autograd.Function):
                  ptr(lg.atom_rowptr), ptr(lg.edge_rev), ptr(lg.rev_trip), ptr(lg.center_order), ptr(alpha), ptr(smax),
                  ptr(sden), ptr(dout), lg.N, lg.max_degree, E, T, heads, channels, ptr(dq), ptr(dk), ptr(dv),
                  ptr(gfold), ptr(d_edge), ptr(g_work), st, *drop)
-            key = lg.atom_type
+            key = None if ctx.route.atom_table else lg.atom_type  # (a per-atom table: d_edge is its gradient)
         else:  # "dst_fold"
             # g[T, H] (d loss / d a_t): the source pass recomputes it from rows it holds anyway (_SRC_G)
             g = None if _SRC_G else torch.empty(T, heads, **f32)
@@ -2417,6 +2456,93 @@ def segment_sum(x, rowptr, num_segments: int, mul=None):
         mul = mul.unsqueeze(1) if mul is not None else None
     out = _SegmentSum.apply(x, mul, _i32(rowptr), int(num_segments))
     return out.squeeze(1) if squeeze else out
+
+
+# ------------------------------------------------------------------- atom context (SBFTransformerV2's edge term)
+# False: the composition segment_sum -> row_chain (3 stages) and their adjoints instead of the fused kernels
+# (tests/test_gpu_model_v2.py flips it); the composition also serves shapes the kernels are not compiled for.
+_ATOM_CTX = True
+
+
+def atom_context_supported(x, linears):
+    """True when x2g_atom_context_fwd / _bwd cover these layers (D = 128 rows of 16-byte aligned fp32)."""
+    if not x.is_cuda or x.dim() != 2 or x.shape[1] != 128 or not rows_fit(x.shape[0], 128):
+        return False
+    for m in linears:
+        if tuple(m.weight.shape) != (128, 128) or m.weight.dtype != torch.float32 or m.weight.data_ptr() % 16:
+            return False
+    return linears[2].bias is None
+
+
+class _AtomContextFn(torch.autograd.Function):
+    """tab [N, D] = lin_edge(edgenn(A)), A[a] = the sum of atom a's out-edge rows of x, in ONE kernel each way
+    (x2g_atom_context_fwd / _bwd, csrc/atom_context.hip).  The forward keeps A, z0, h and g: A, h and g are the
+    row-major x operands of the three weight gradients, z0 is where SiLU' is taken.  The backward leaves d_g and
+    d_z0 row-major; the five weight / bias gradients are row-major jobs of the flat launch (tiled_wgrad).  The
+    layer input's gradient joins its fan-in buffer through the kernel's accumulate flag."""
+
+    @staticmethod
+    def forward(ctx, x, rowptr, n_atoms, w0, b0, w1, b1, we):
+        x2 = _f32(x)
+        E, D = x2.shape
+        N = int(n_atoms)
+        f32 = dict(dtype=torch.float32, device=x2.device)
+        grad = _keeps(ctx)
+        W0, W1, We = _f32(w0), _f32(w1), _f32(we)
+        B0 = _f32(b0) if b0 is not None else None
+        B1 = _f32(b1) if b1 is not None else None
+        tab = torch.empty(N, D, **f32)
+        kept = [torch.empty(N, D, **f32) if grad else None for _ in range(4)]  # A, z0, h, g
+        call("x2g_atom_context_fwd", ptr(x2), ptr(rowptr), N, E, D, ptr(W0), ptr(B0), ptr(W1), ptr(B1), ptr(We),
+             ptr(tab), *[ptr(t) for t in kept], stream_ptr())
+        if grad:
+            ctx.save_for_backward(*kept, W0, W1, We, rowptr)
+        ctx.rows = E
+        ctx.params = (w0, b0, w1, b1, we)
+        ctx.fan = _fan_of(x)
+        return tab
+
+    @staticmethod
+    def backward(ctx, d_tab):
+        A, z0, h, g, W0, W1, We, rowptr = ctx.saved_tensors
+        d_tab = _f32(d_tab)
+        N, D = d_tab.shape
+        E = ctx.rows
+        f32 = dict(dtype=torch.float32, device=d_tab.device)
+        d_g, d_z0 = torch.empty(N, D, **f32), torch.empty(N, D, **f32)
+        dx, first = None, True
+        if ctx.needs_input_grad[0]:
+            if ctx.fan is not None:  # add into the layer input's fan-in buffer
+                dx, first = ctx.fan.take((E, D), d_tab.device)
+            else:
+                dx = torch.empty(E, D, **f32)
+        call("x2g_atom_context_bwd", ptr(d_tab), ptr(z0), ptr(rowptr), N, E, D, ptr(W0), ptr(W1), ptr(We), ptr(d_g),
+             ptr(d_z0), ptr(dx), 0 if first else 1, stream_ptr())
+        w0, b0, w1, b1, we = ctx.params
+        rm = TILED_DY_ROWMAJOR | TILED_X_ROWMAJOR
+        (dwe, dw1, dw0), (_, db1, db0) = tiled_wgrad([d_tab, d_g, d_z0], [g, h, A], N, [we, w1, w0], [None, b1, b0],
+                                                     layouts=[rm, rm, rm])
+        return dx if first else None, None, None, dw0, db0, dw1, db1, dwe
+
+
+def atom_context(x, atom_rowptr, edge_src, edgenn_lin0, edgenn_lin1, lin_edge):
+    """SBFTransformerV2's per-layer edge table [N, D] = lin_edge(edgenn_lin1(SiLU(edgenn_lin0(A)))) with
+    A = scatter_add(x, edge_src) over the N = len(atom_rowptr) - 1 atoms (reference model.py:138-141 with
+    sbftransformer_conv.py:144, per atom instead of per triplet).  ``atom_rowptr``: each atom's out-edge line
+    nodes are the contiguous rows [atom_rowptr[a], atom_rowptr[a + 1]) of x; ``edge_src``: the same as an index
+    per row (read by the host-tensor form only)."""
+    N = int(atom_rowptr.shape[0]) - 1
+    lins = [edgenn_lin0, edgenn_lin1, lin_edge]
+    if not x.is_cuda:  # modules built and run on a host (Linear.fused's plain nn.Linear math)
+        A = torch.zeros(N, x.shape[1], dtype=x.dtype).index_add_(0, edge_src.long(), x)
+        return lin_edge(edgenn_lin1(torch.nn.functional.silu(edgenn_lin0(A))))
+    if _ATOM_CTX and atom_context_supported(x, lins):
+        return _apply(_AtomContextFn, x, _i32(atom_rowptr), N, edgenn_lin0.weight, edgenn_lin0.bias,
+                      edgenn_lin1.weight, edgenn_lin1.bias, lin_edge.weight)
+    A = segment_sum(x, atom_rowptr, N)
+    if _CHAIN and chain_supported(A, lins):
+        return row_chain(A, None, lins, [CHAIN_SILU, 0, 0])
+    return lin_edge.fused(edgenn_lin1.fused(edgenn_lin0.fused(A, act=ACT_SILU)))
 
 
 class IndexPlan:

@@ -100,6 +100,8 @@ class GraphPlan:
         if p.lg.atom_type is None:
             p.lg.atom_type = ops._i32(data.x.reshape(-1))
         p.lg.dst_type, p.lg.src_type = p.dst_type, src_type
+        # a per-atom edge table's rows (SBFTransformerV2): the line nodes' destination / source atoms themselves
+        p.lg.dst_atom, p.lg.src_atom = p.lg.edge_dst, p.lg.edge_src
         p.atom_rowptr = p.lg.atom_rowptr
         # per-molecule line-node / triplet counts on the host: whole-molecule ranges of the triplet
         # stream for the tiled inference attention (ops._infer_tiles), with no device read; the atoms

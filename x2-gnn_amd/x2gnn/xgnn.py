@@ -22,7 +22,7 @@ from torch.nn import SiLU
 from . import ops
 from .data import Data
 from .layers import EmbeddingBlock, F_B_2D, Linear, RadialBasis, poly_envelop
-from .model import SBFTransformer, SBFTransformerGlobal, SBFTransformerMulti
+from .model import SBFTransformer, SBFTransformerGlobal, SBFTransformerMulti, SBFTransformerV2
 from .plan import GraphPlan
 
 
@@ -72,15 +72,21 @@ class _XGNNBase(nn.Module):
             neo_x = self.mat_trans.fused(data.edge_attr * env, act=ops.ACT_SILU)
         # under molecule sharding the embedding's per-batch rules count the global batch's atoms
         # (dist.collate_shard); otherwise this batch's
-        table, edge_proj = self._edge_tables(data.x, data._store.get("_x2g_count_z"))
+        edge_term, edge_proj = self._edge_term(data, plan)
         sbf = self.sbf_layer.from_positions(dist, pos, lg, bessel, lazy=lazy_sbf)
         if not fused_feat:
             neo_x = self.emb_trans.fused(neo_x, act=ops.ACT_SILU)
-        line = Data(x=neo_x, edge_attr=table, edge_attr_row=plan.dst_type, edge_sbf=sbf, node_rbf=node_rbf)
+        line = Data(x=neo_x, edge_sbf=sbf, node_rbf=node_rbf, **edge_term)
         line._store["_x2g_plan"] = plan
         if edge_proj is not None:
             line._store["_x2g_edge_proj"] = edge_proj
         return line, plan
+
+    def _edge_term(self, data, plan):
+        """(the line-graph Data's edge-term fields, per-layer lin_edge tables or None): the element table and the
+        row of it each line node's triplets read (xgnn.py:57-58)."""
+        table, edge_proj = self._edge_tables(data.x, data._store.get("_x2g_count_z"))
+        return dict(edge_attr=table, edge_attr_row=plan.dst_type), edge_proj
 
     def _edge_tables(self, atomic_num, count_z=None):
         """(element table, per-layer lin_edge tables or None).  The embedding Linear, edgenn and every
@@ -141,3 +147,22 @@ class xgnn_poly_multi(_XGNNBase):
                                     mol_targets=mol_targets, pool_option=pool_option, attn_dropout=attn_dropout,
                                     dropout_seed=dropout_seed, beta=conv_beta)
         self._build(trunk, sbf_dim, rbf_dim, in_channels, embedding_size, device)
+
+
+class xgnn_poly_v2(_XGNNBase):
+    """xgnn_poly's featurisation in front of SBFTransformerV2 (reference model.py:100-150), whose edge term is
+    recomputed per layer from the line-node features pooled per atom.  V2 reads no element embedding, so there is
+    no ``emb_block``: the per-triplet ``edge_attr`` is the triplet's middle atom (what ``atom_embeddings[atom_j]``,
+    xgnn.py:57-58, indexes), and ``edge_atom_row`` the same atom per destination line node (the plan's
+    ``edge_dst``), which lets the trunk run the chain on the atom rows."""
+
+    def __init__(self, conv_layers=4, sbf_dim=7, rbf_dim=16, in_channels=128, heads=16, embedding_size=128,
+                 device="cpu"):
+        super().__init__()
+        trunk = SBFTransformerV2(conv_layers=conv_layers, emb_size=embedding_size, sbf_dim=sbf_dim, rbf_dim=rbf_dim,
+                                 in_channels=in_channels, heads=heads)
+        self._build(trunk, sbf_dim, rbf_dim, in_channels, embedding_size, device)
+        del self.emb_block
+
+    def _edge_term(self, data, plan):
+        return dict(edge_attr=plan.lg.atom_j, edge_atom_row=plan.lg.edge_dst), None
