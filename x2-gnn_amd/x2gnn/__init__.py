@@ -7,16 +7,19 @@ Device side: ``libx2g.so`` (hand-written gfx950 HIP kernels behind the C ABI in
 """
 from .data import Batch, Data, collate, molecule_to_data
 from .device_dataset import DeviceDataset
+from .fit import fit
+from .init import reference_init_
 from .layers import AtomWise, EmbeddingBlock, F_B_2D, MolWise, RadialBasis, ResidualLayer, poly_envelop
 from .model import LayerNorm, SBFTransformer, SBFTransformerGlobal, SBFTransformerMulti, SBFTransformerV2
 from .plan import GraphPlan
 from .sbftransformer_conv import SBFTransformerConv
+from .schedule import Plateau
 from .train import Evaluator, Inference, Trainer
 from .xgnn import xgnn_poly, xgnn_poly_global, xgnn_poly_multi, xgnn_poly_v2
 
 __all__ = [
     "AtomWise", "Batch", "Data", "DeviceDataset", "EmbeddingBlock", "Evaluator", "F_B_2D", "GraphPlan", "Inference",
-    "LayerNorm", "MolWise", "RadialBasis", "ResidualLayer", "SBFTransformer", "SBFTransformerConv",
-    "SBFTransformerGlobal", "SBFTransformerMulti", "SBFTransformerV2", "Trainer", "collate", "molecule_to_data",
-    "poly_envelop", "xgnn_poly", "xgnn_poly_global", "xgnn_poly_multi", "xgnn_poly_v2",
+    "LayerNorm", "MolWise", "Plateau", "RadialBasis", "ResidualLayer", "SBFTransformer", "SBFTransformerConv",
+    "SBFTransformerGlobal", "SBFTransformerMulti", "SBFTransformerV2", "Trainer", "collate", "fit", "molecule_to_data",
+    "poly_envelop", "reference_init_", "xgnn_poly", "xgnn_poly_global", "xgnn_poly_multi", "xgnn_poly_v2",
 ]

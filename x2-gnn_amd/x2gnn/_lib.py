@@ -29,6 +29,8 @@ MULTI_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_multi.h")
 CONV_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_conv.h")
 # the atom-context chain's header (SBFTransformerV2's per-layer edge term): a table of its own as well
 ATOMCTX_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_atomctx.h")
+# the guarded parameter update's header (FlatAdam(skip_nonfinite=True)): one more table of its own
+TRAIN_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_train.h")
 
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int": ctypes.c_int,
             "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
@@ -139,6 +141,8 @@ MULTI_SIGNATURES, MULTI_RESTYPES = _read_functions(MULTI_HEADER_PATH)
 CONV_SIGNATURES, CONV_RESTYPES = _read_functions(CONV_HEADER_PATH, known=tuple(STRUCTS))
 # and for the atom-context chain (x2g_atomctx.h)
 ATOMCTX_SIGNATURES, ATOMCTX_RESTYPES = _read_functions(ATOMCTX_HEADER_PATH)
+# and for the guarded parameter update (x2g_train.h)
+TRAIN_SIGNATURES, TRAIN_RESTYPES = _read_functions(TRAIN_HEADER_PATH)
 
 _lib = None
 
@@ -155,7 +159,8 @@ def load():
             fn.argtypes = args
             fn.restype = RESTYPES[name]
         for sigs, res in ((STAGED_SIGNATURES, STAGED_RESTYPES), (MULTI_SIGNATURES, MULTI_RESTYPES),
-                          (CONV_SIGNATURES, CONV_RESTYPES), (ATOMCTX_SIGNATURES, ATOMCTX_RESTYPES)):
+                          (CONV_SIGNATURES, CONV_RESTYPES), (ATOMCTX_SIGNATURES, ATOMCTX_RESTYPES),
+                          (TRAIN_SIGNATURES, TRAIN_RESTYPES)):
             for name, args in sigs.items():
                 # (a library built from an earlier tree, X2G_LIB, has none of them: calling one then raises)
                 fn = getattr(lib, name, None)

@@ -360,3 +360,15 @@ def model_for_target(target: int, cfg: dict, device="cuda", pool_option="mean"):
     if target in ATOMWISE_TARGETS:
         return xgnn_poly(device=device, **cfg)
     return xgnn_poly_global(device=device, pool_option=pool_option, **cfg)
+
+
+def split_indices(n: int, division, seed: int):
+    """The reference's split (trainer.py:22-27): ``(test, val, train)`` int64 index arrays, ``perm[:division[0]]``,
+    ``perm[division[0]:division[1]]`` and ``perm[division[1]:]`` of ``perm = RandomState(seed).permutation(n)``:
+    the stream ``np.random.seed(seed); np.random.permutation(n)`` gives, drawn from a generator of its own, so
+    numpy's global state is not touched."""
+    a, b = int(division[0]), int(division[1])
+    if not 0 <= a <= b <= n:
+        raise ValueError(f"division {tuple(division)} does not cut a dataset of {n}")
+    perm = np.random.RandomState(seed).permutation(n).astype(np.int64)
+    return perm[:a], perm[a:b], perm[b:]

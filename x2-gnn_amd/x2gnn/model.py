@@ -94,9 +94,10 @@ class _ReadoutFamily:
         return results
 
 
-def glorot_ortho_(tensor, scale=2.0):
-    """The reference's ``Glorot_Ortho_`` (initializer.py:29-35): orthogonal, rescaled to the Glorot variance."""
-    nn.init.orthogonal_(tensor)
+def glorot_ortho_(tensor, scale=2.0, generator=None):
+    """The reference's ``Glorot_Ortho_`` (initializer.py:29-35): orthogonal, rescaled to the Glorot variance.
+    ``generator``: where the draws come from (None: torch's global generator, as the reference)."""
+    nn.init.orthogonal_(tensor, generator=generator)
     with torch.no_grad():
         tensor.mul_(torch.sqrt(scale / ((tensor.shape[0] + tensor.shape[1]) * tensor.var())))
     return tensor

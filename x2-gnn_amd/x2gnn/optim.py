@@ -27,10 +27,20 @@ class FlatAdam:
 
     ``params`` must all be fp32 CUDA tensors; they become views of ``self.flat`` (values kept).
     ``ema`` (a flat buffer, same layout) holds the AveragedModel parameters; ``ema_params()``
-    returns them shaped like the model's parameters."""
+    returns them shaped like the model's parameters.
+
+    ``skip_nonfinite=True``: every ``step`` is the guarded update (``x2g_clip_adam_ema_guard``,
+    include/x2g_train.h).  A step whose gradient norm is inf or NaN (an inf / NaN gradient, or finite gradients
+    whose sum of squares overflows fp32, a norm above about 1.8e19) is skipped on the device: parameters, both
+    moments, the average, the step count and the learning-rate schedule stay as they were, the gradients are
+    still zeroed when asked, and ``skipped`` / ``last_skipped`` (device int64 scalars, allocated here) count it.
+    A step with a finite norm writes bit for bit what the unguarded one writes.  The decision needs no host read,
+    so it holds inside a captured graph.  Under data parallelism every rank holds the same reduced bucket, forms
+    the same norm and reaches the same verdict: no collective is added.  With the default ``False``, ``step``
+    makes the one call it always made and nothing is allocated."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_norm=100.0, ema_decay=0.95,
-                 bucket: GradBucket | None = None):
+                 bucket: GradBucket | None = None, skip_nonfinite=False):
         self.params = [p for p in params if p.requires_grad]
         dev = self.params[0].device
         self.offsets, n = flat_layout(self.params)  # same layout as GradBucket: 16-byte aligned views
@@ -49,12 +59,23 @@ class FlatAdam:
         sc[[_LR, _B1, _B2, _EPS, _MAXN, _EMAD]] = torch.tensor(
             [lr, betas[0], betas[1], eps, max_norm if max_norm else 0.0, ema_decay or 0.0], dtype=torch.float32)
         self.scalars = sc.to(dev)
-        self.ws_bytes = int(_lib.load().x2g_optimizer_workspace(n))
+        self.skip_nonfinite = bool(skip_nonfinite)
+        # [skipped steps, whether the last step was skipped]: written by the guarded update only
+        self.guard = torch.zeros(2, dtype=torch.int64, device=dev) if self.skip_nonfinite else None
+        lib = _lib.load()
+        self.ws_bytes = int((lib.x2g_optimizer_guard_workspace if self.skip_nonfinite
+                             else lib.x2g_optimizer_workspace)(n))
         self.ws = torch.empty(max(self.ws_bytes, 4), dtype=torch.uint8, device=dev)
 
     def step(self, zero_grads=False):
         """One update; ``zero_grads``: also zero the gradient bucket as it is read (zero_grad()
         folded into the step's last kernel, so the next backward needs no fill)."""
+        if self.skip_nonfinite:
+            call("x2g_clip_adam_ema_guard", ptr(self.flat), ptr(self.bucket.flat), ptr(self.exp_avg),
+                 ptr(self.exp_avg_sq), ptr(self.ema), self.flat.numel(), ptr(self.scalars),
+                 _lib.CONSTS["OPT_ZERO_GRADS"] if zero_grads else 0, ptr(self.guard), ptr(self.ws), self.ws_bytes,
+                 stream_ptr())
+            return
         call("x2g_clip_adam_ema_ex", ptr(self.flat), ptr(self.bucket.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq),
              ptr(self.ema), self.flat.numel(), ptr(self.scalars),
              _lib.CONSTS["OPT_ZERO_GRADS"] if zero_grads else 0, ptr(self.ws), self.ws_bytes, stream_ptr())
@@ -90,6 +111,22 @@ class FlatAdam:
     @property
     def steps(self):
         return self.scalars[_STEP]
+
+    @property
+    def skipped(self):
+        """The steps the guard has skipped (device int64 scalar; a per-run diagnostic, not part of any saved
+        state).  Without ``skip_nonfinite`` there is no guard: ValueError."""
+        return self._guard_word(0)
+
+    @property
+    def last_skipped(self):
+        """Whether the last step was skipped (device int64 scalar, 0 or 1)."""
+        return self._guard_word(1)
+
+    def _guard_word(self, i):
+        if self.guard is None:
+            raise ValueError("this optimizer has no guard (skip_nonfinite=False)")
+        return self.guard[i]
 
     def ema_params(self):
         return [self.ema[off:off + p.numel()].view_as(p) for p, off in zip(self.params, self.offsets)]

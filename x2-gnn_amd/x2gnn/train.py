@@ -47,12 +47,14 @@ class Trainer:
     (host ints from the sharding); None = every rank holds the same count (plain mean)."""
 
     def __init__(self, model, lr=1e-3, max_norm=100.0, ema_decay=0.95, local_count=None, global_count=None,
-                 group=None, lr_schedule=None, exchange_chunks=1):
+                 group=None, lr_schedule=None, exchange_chunks=1, skip_nonfinite=False):
         """``lr_schedule``: None (constant ``lr``) or a dict of LinearWarmupExponentialDecay's
         arguments — warmup_steps, decay_steps, decay_rate[, staircase] (config.json: 3000, 3e6,
         0.01) — applied per step from base ``lr`` (FlatAdam.set_schedule).  ``exchange_chunks``: the
         gradient all-reduce as that many asynchronous collectives over contiguous bucket ranges
-        (GradBucket.allreduce_mean(chunks=...)), joined before the optimizer."""
+        (GradBucket.allreduce_mean(chunks=...)), joined before the optimizer.  ``skip_nonfinite``: the update
+        skips, on the device, a step whose gradient norm is not finite (FlatAdam; ``opt.skipped`` counts them;
+        the count is a per-run diagnostic and is not part of ``state_dict``)."""
         self.model = model
         self.group = group
         self.multi = _world(group) > 1
@@ -60,7 +62,8 @@ class Trainer:
         self.bucket = GradBucket(model.parameters(), extra=1 if self.multi else 0)
         # clip_grad_norm_(100) + Adam(1e-3) + EMA(0.95) (config.json) in three launches over the
         # flat parameter / gradient buffers (x2gnn.optim.FlatAdam, csrc/optim.hip)
-        self.opt = FlatAdam(model.parameters(), lr=lr, max_norm=max_norm, ema_decay=ema_decay, bucket=self.bucket)
+        self.opt = FlatAdam(model.parameters(), lr=lr, max_norm=max_norm, ema_decay=ema_decay, bucket=self.bucket,
+                            skip_nonfinite=skip_nonfinite)
         if lr_schedule is not None:
             self.opt.set_schedule(base_lr=lr, **lr_schedule)
         self.flat_launches = []  # [(rows, cols) per job] of the last backward's flat weight-gradient launches
