@@ -7,6 +7,7 @@ Device side: ``libx2g.so`` (hand-written gfx950 HIP kernels behind the C ABI in
 """
 from .data import Batch, Data, collate, molecule_to_data
 from .device_dataset import DeviceDataset
+from .features import AOMatrices, ao_edge_features, bi_gen_edge_feature_6
 from .fit import fit
 from .init import reference_init_
 from .layers import AtomWise, EmbeddingBlock, F_B_2D, MolWise, RadialBasis, ResidualLayer, poly_envelop
@@ -18,8 +19,9 @@ from .train import Evaluator, Inference, Trainer
 from .xgnn import xgnn_poly, xgnn_poly_global, xgnn_poly_multi, xgnn_poly_v2
 
 __all__ = [
-    "AtomWise", "Batch", "Data", "DeviceDataset", "EmbeddingBlock", "Evaluator", "F_B_2D", "GraphPlan", "Inference",
-    "LayerNorm", "MolWise", "Plateau", "RadialBasis", "ResidualLayer", "SBFTransformer", "SBFTransformerConv",
-    "SBFTransformerGlobal", "SBFTransformerMulti", "SBFTransformerV2", "Trainer", "collate", "fit", "molecule_to_data",
-    "poly_envelop", "reference_init_", "xgnn_poly", "xgnn_poly_global", "xgnn_poly_multi", "xgnn_poly_v2",
+    "AOMatrices", "AtomWise", "Batch", "Data", "DeviceDataset", "EmbeddingBlock", "Evaluator", "F_B_2D", "GraphPlan",
+    "Inference", "LayerNorm", "MolWise", "Plateau", "RadialBasis", "ResidualLayer", "SBFTransformer",
+    "SBFTransformerConv", "SBFTransformerGlobal", "SBFTransformerMulti", "SBFTransformerV2", "Trainer",
+    "ao_edge_features", "bi_gen_edge_feature_6", "collate", "fit", "molecule_to_data", "poly_envelop",
+    "reference_init_", "xgnn_poly", "xgnn_poly_global", "xgnn_poly_multi", "xgnn_poly_v2",
 ]

@@ -31,6 +31,8 @@ CONV_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_conv.h")
 ATOMCTX_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_atomctx.h")
 # the guarded parameter update's header (FlatAdam(skip_nonfinite=True)): one more table of its own
 TRAIN_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_train.h")
+# the AO edge features' header (x2gnn.features: the model's input from S and H_core): a table of its own, like the rest
+FEATURES_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_features.h")
 
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int": ctypes.c_int,
             "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
@@ -143,6 +145,8 @@ CONV_SIGNATURES, CONV_RESTYPES = _read_functions(CONV_HEADER_PATH, known=tuple(S
 ATOMCTX_SIGNATURES, ATOMCTX_RESTYPES = _read_functions(ATOMCTX_HEADER_PATH)
 # and for the guarded parameter update (x2g_train.h)
 TRAIN_SIGNATURES, TRAIN_RESTYPES = _read_functions(TRAIN_HEADER_PATH)
+# and for the AO edge features (x2g_features.h)
+FEATURES_SIGNATURES, FEATURES_RESTYPES = _read_functions(FEATURES_HEADER_PATH)
 
 _lib = None
 
@@ -160,7 +164,7 @@ def load():
             fn.restype = RESTYPES[name]
         for sigs, res in ((STAGED_SIGNATURES, STAGED_RESTYPES), (MULTI_SIGNATURES, MULTI_RESTYPES),
                           (CONV_SIGNATURES, CONV_RESTYPES), (ATOMCTX_SIGNATURES, ATOMCTX_RESTYPES),
-                          (TRAIN_SIGNATURES, TRAIN_RESTYPES)):
+                          (TRAIN_SIGNATURES, TRAIN_RESTYPES), (FEATURES_SIGNATURES, FEATURES_RESTYPES)):
             for name, args in sigs.items():
                 # (a library built from an earlier tree, X2G_LIB, has none of them: calling one then raises)
                 fn = getattr(lib, name, None)

@@ -53,6 +53,12 @@ class Data:
     def __contains__(self, key):
         return key in self._store
 
+    def __getitem__(self, key):
+        return self._store[key]
+
+    def get(self, key, default=None):
+        return self._store.get(key, default)
+
     def keys(self):
         return list(self._store.keys())
 

@@ -13,8 +13,12 @@
   ``Label`` is [1, 12] so a collate stacks it to [M, 12] (train_ema.py:32 indexes ``y[:, t]``).
 * ``record_to_data`` — qm9_allprop.py:11-19's ``mapping`` minus the pyscf features: the
   distance matrix of atom_graph.py:32-35 (float32 Gram form) and ``gen_bonds_mini``'s
-  ``argwhere((D < cutoff) & D != 0)`` (atom_graph.py:42-45).  ``edge_attr`` must be supplied
-  (pyscf is not available); :func:`synthetic_edge_attr` gives the seeded stand-in.
+  ``argwhere((D < cutoff) & D != 0)`` (atom_graph.py:42-45).  ``edge_attr`` is supplied, or
+  :func:`synthetic_edge_attr` gives the seeded stand-in.
+* ``records_to_data`` — the whole ``mapping`` for a list of records whose overlap and
+  core-Hamiltonian matrices are at hand (:class:`x2gnn.features.AOMatrices`, from pyscf elsewhere
+  or from a file): the same bonds, and the real ``edge_attr`` of scf.py:50-119 computed on the
+  device, many molecules per launch.  Only the integrals themselves (``geom_scf_6``) need pyscf.
 * ``load_collated`` — a PyG ``InMemoryDataset`` processed file (qm9_allprop.py:58,
   ``torch.save(self.collate(datas), ...)`` = a pickled ``(Data, slices)`` under PyG 2.1.0) read
   with ``torch.load(weights_only=True)``: the PyG classes the pickle names are allow-listed as
@@ -185,6 +189,47 @@ def record_to_data(rec: MolRecord, edge_attr: torch.Tensor | None = None, cutoff
     object.__setattr__(d, "_meta", {"nodes": np.array([rec.Z.shape[0]]), "edges": np.array([ei.shape[1]]),
                                     "triplets": np.array([triplet_count(ei.numpy(), rec.Z.shape[0])])})
     return d
+
+
+def records_to_data(records, ao, device, cutoff: float = 5.0, max_edges_per_launch: int = 1 << 18) -> list:
+    """qm9_allprop.py:11-19 ``mapping`` for every record, with the features made on ``device`` from ``ao``
+    (:class:`x2gnn.features.AOMatrices`, molecule k belonging to ``records[k]``).  Bonds are
+    :func:`record_to_data`'s; the reference's check ``aoslice.shape[0] == edge_index.max() + 1``
+    (qm9_allprop.py:15) raises ValueError naming the record.  As many whole molecules as fit
+    ``max_edges_per_launch`` edges share one launch (a molecule with more edges than that gets one of its own);
+    only their matrices are on the device at a time.  Each ``Data`` carries its CPU float32 ``edge_attr`` slice."""
+    from .features import ao_edge_features
+
+    records = list(records)
+    if len(ao) != len(records):
+        raise ValueError(f"{len(ao)} molecules of AO matrices for {len(records)} records")
+    atom_start = ao.atom_start.numpy()
+    eis = []
+    for k, rec in enumerate(records):
+        ei = bonds(distance_matrix(rec.R), cutoff)
+        n_ao = int(atom_start[k + 1] - atom_start[k])
+        top = int(ei.max()) + 1 if ei.shape[1] else int(rec.Z.shape[0])
+        if n_ao != top:
+            raise ValueError(f"record {k} (idx {int(rec.idx.reshape(-1)[0])}): aoslice has {n_ao} atoms, the bonds "
+                             f"reach atom {top - 1}")
+        eis.append(ei)
+    out, lo = [], 0
+    while lo < len(records):
+        hi, total = lo + 1, eis[lo].shape[1]
+        while hi < len(records) and total + eis[hi].shape[1] <= max_edges_per_launch:
+            total += eis[hi].shape[1]
+            hi += 1
+        part = ao.slice(lo, hi).to(device)
+        offs = atom_start[lo:hi] - atom_start[lo]
+        ei_all = torch.cat([ei + int(o) for ei, o in zip(eis[lo:hi], offs)], dim=1)
+        attr = ao_edge_features(part, ei_all.to(device), part.atom_mol()).cpu()
+        at = 0
+        for k in range(lo, hi):
+            E = eis[k].shape[1]
+            out.append(record_to_data(records[k], attr[at:at + E].clone(), cutoff))
+            at += E
+        lo = hi
+    return out
 
 
 # ---------------------------------------------------------------------------------- PyG .pt files
