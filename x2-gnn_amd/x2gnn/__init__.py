@@ -9,6 +9,7 @@ from .data import Batch, Data, collate, molecule_to_data
 from .device_dataset import DeviceDataset
 from .features import AOMatrices, ao_edge_features, bi_gen_edge_feature_6
 from .fit import fit
+from .graph import radius_graph
 from .init import reference_init_
 from .layers import AtomWise, EmbeddingBlock, F_B_2D, MolWise, RadialBasis, ResidualLayer, poly_envelop
 from .model import LayerNorm, SBFTransformer, SBFTransformerGlobal, SBFTransformerMulti, SBFTransformerV2
@@ -23,5 +24,5 @@ __all__ = [
     "Inference", "LayerNorm", "MolWise", "Plateau", "RadialBasis", "ResidualLayer", "SBFTransformer",
     "SBFTransformerConv", "SBFTransformerGlobal", "SBFTransformerMulti", "SBFTransformerV2", "Trainer",
     "ao_edge_features", "bi_gen_edge_feature_6", "collate", "fit", "molecule_to_data", "poly_envelop",
-    "reference_init_", "xgnn_poly", "xgnn_poly_global", "xgnn_poly_multi", "xgnn_poly_v2",
+    "radius_graph", "reference_init_", "xgnn_poly", "xgnn_poly_global", "xgnn_poly_multi", "xgnn_poly_v2",
 ]

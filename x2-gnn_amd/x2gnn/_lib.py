@@ -33,6 +33,8 @@ ATOMCTX_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_atomctx.h"
 TRAIN_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_train.h")
 # the AO edge features' header (x2gnn.features: the model's input from S and H_core): a table of its own, like the rest
 FEATURES_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_features.h")
+# the radius graph's header (x2gnn.graph: bonds and per-molecule counts from positions): a table of its own too
+GRAPH_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_graph.h")
 
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int": ctypes.c_int,
             "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
@@ -147,6 +149,8 @@ ATOMCTX_SIGNATURES, ATOMCTX_RESTYPES = _read_functions(ATOMCTX_HEADER_PATH)
 TRAIN_SIGNATURES, TRAIN_RESTYPES = _read_functions(TRAIN_HEADER_PATH)
 # and for the AO edge features (x2g_features.h)
 FEATURES_SIGNATURES, FEATURES_RESTYPES = _read_functions(FEATURES_HEADER_PATH)
+# and for the radius graph (x2g_graph.h)
+GRAPH_SIGNATURES, GRAPH_RESTYPES = _read_functions(GRAPH_HEADER_PATH)
 
 _lib = None
 
@@ -164,7 +168,8 @@ def load():
             fn.restype = RESTYPES[name]
         for sigs, res in ((STAGED_SIGNATURES, STAGED_RESTYPES), (MULTI_SIGNATURES, MULTI_RESTYPES),
                           (CONV_SIGNATURES, CONV_RESTYPES), (ATOMCTX_SIGNATURES, ATOMCTX_RESTYPES),
-                          (TRAIN_SIGNATURES, TRAIN_RESTYPES), (FEATURES_SIGNATURES, FEATURES_RESTYPES)):
+                          (TRAIN_SIGNATURES, TRAIN_RESTYPES), (FEATURES_SIGNATURES, FEATURES_RESTYPES),
+                          (GRAPH_SIGNATURES, GRAPH_RESTYPES)):
             for name, args in sigs.items():
                 # (a library built from an earlier tree, X2G_LIB, has none of them: calling one then raises)
                 fn = getattr(lib, name, None)

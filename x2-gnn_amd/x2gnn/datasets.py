@@ -19,6 +19,8 @@
   core-Hamiltonian matrices are at hand (:class:`x2gnn.features.AOMatrices`, from pyscf elsewhere
   or from a file): the same bonds, and the real ``edge_attr`` of scf.py:50-119 computed on the
   device, many molecules per launch.  Only the integrals themselves (``geom_scf_6``) need pyscf.
+  (``DeviceDataset.from_records`` builds the same dataset with the bonds made on the device too,
+  :mod:`x2gnn.graph`, and no feature row on the host.)
 * ``load_collated`` — a PyG ``InMemoryDataset`` processed file (qm9_allprop.py:58,
   ``torch.save(self.collate(datas), ...)`` = a pickled ``(Data, slices)`` under PyG 2.1.0) read
   with ``torch.load(weights_only=True)``: the PyG classes the pickle names are allow-listed as

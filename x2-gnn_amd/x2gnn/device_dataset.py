@@ -110,6 +110,87 @@ class DeviceDataset:
                    y.to(torch.float32).numpy(), device)
         return self
 
+    @classmethod
+    def from_records(cls, records, ao, device, cutoff=5.0, max_edges_per_launch=1 << 18):
+        """The dataset ``DeviceDataset(datasets.records_to_data(records, ao, device, cutoff), device)`` builds, every
+        device tensor and every host cache equal, made without that path's round trip: ``x``, ``atom_pos`` and ``y``
+        are uploaded once, one :func:`x2gnn.graph.radius_graph` call makes the bonds of the whole set on the device,
+        ``edge_attr`` is allocated once there and filled through ``ao_edge_features(out=...)`` (as many whole
+        molecules as fit ``max_edges_per_launch`` edges per launch, only their matrices on the device at a time),
+        and the caches are the kernel's per-molecule counts: no recount, ``symmetric`` all True by construction, no
+        feature row ever on the host.
+
+        ``records``: :class:`x2gnn.datasets.MolRecord`; ``ao``: :class:`x2gnn.features.AOMatrices`, molecule k
+        belonging to ``records[k]``.  The reference's check ``aoslice.shape[0] == edge_index.max() + 1``
+        (qm9_allprop.py:15; the atom count for a molecule without an edge) raises ValueError naming the record
+        before any feature launch, a molecule count that differs raises ValueError, and a device that is no GPU
+        raises RuntimeError: there is no CPU implementation."""
+        from .features import ao_edge_features
+        from .graph import radius_graph
+        from .synth import EDGE_FEATURES
+
+        records = list(records)
+        if len(ao) != len(records):
+            raise ValueError(f"{len(ao)} molecules of AO matrices for {len(records)} records")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"DeviceDataset.from_records needs a GPU, got device {device} (no CPU fallback by "
+                               f"design; datasets.records_to_data is the reference's path)")
+        M = len(records)
+        nodes = np.fromiter((int(r.Z.shape[0]) for r in records), dtype=np.int64, count=M)
+
+        def cat(parts, dtype, tail):
+            return np.concatenate(parts) if parts else np.zeros((0,) + tail, dtype)
+
+        x = cat([np.asarray(r.Z, dtype=np.int64).reshape(-1) for r in records], np.int64, ())
+        pos = cat([np.asarray(r.R.to(torch.float32), dtype=np.float32).reshape(-1, 3) for r in records], np.float32,
+                  (3,))
+        y = molecule_targets([{"y": r.Label} for r in records])
+        if int(nodes.sum()) != len(x) or len(pos) != len(x):
+            raise ValueError("per-molecule sizes do not match the concatenated tensors")
+
+        self = cls.__new__(cls)
+        self.device = device
+        self.nodes = nodes
+        self.atom_start = np.concatenate([[0], np.cumsum(nodes)]).astype(np.int64)
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+        self.x, self.atom_pos, self.y = up(x), up(pos), up(y)
+        g = radius_graph(self.atom_pos, self.atom_start, cutoff)
+        ao_start = ao.atom_start.numpy().astype(np.int64)
+        top = np.where(g.last_bonded >= 0, g.last_bonded.astype(np.int64) + 1, nodes)
+        bad = np.flatnonzero(np.diff(ao_start) != top)
+        if bad.size:
+            k = int(bad[0])
+            raise ValueError(f"record {k} (idx {int(records[k].idx.reshape(-1)[0])}): aoslice has "
+                             f"{int(ao_start[k + 1] - ao_start[k])} atoms, the bonds reach atom {int(top[k]) - 1}")
+        self.edges, self.triplets, self.max_degree = g.edges, g.triplets, g.max_degree
+        self.symmetric = np.ones(M, bool)  # the edge test is bitwise symmetric in (i, j): every edge has its reverse
+        self.edge_start = np.concatenate([[0], np.cumsum(self.edges)]).astype(np.int64)
+        self.edge_index = g.edge_index
+        self.num_features = EDGE_FEATURES if M else 0
+        self.edge_attr = (torch.empty((int(self.edge_start[-1]), EDGE_FEATURES), dtype=torch.float32, device=device)
+                          if M else None)
+        lo = 0
+        while lo < M:
+            hi, total = lo + 1, int(self.edges[lo])
+            while hi < M and total + int(self.edges[hi]) <= max_edges_per_launch:
+                total += int(self.edges[hi])
+                hi += 1
+            if total:
+                e0, e1 = int(self.edge_start[lo]), int(self.edge_start[hi])
+                part = ao.slice(lo, hi).to(device)
+                # local ids -> the chunk's atom numbering, which is the matrices' (ao.atom_start), not the records'
+                shift = torch.repeat_interleave(up(ao_start[lo:hi] - ao_start[lo]), up(self.edges[lo:hi]),
+                                                output_size=total)
+                ao_edge_features(part, self.edge_index[:, e0:e1] + shift, part.atom_mol(), out=self.edge_attr[e0:e1])
+            lo = hi
+        self.mol_trips = up(self.triplets)
+        self._stage, self._slot, self._debug_fill = None, 0, None
+        return self
+
     def _init(self, nodes, edges, x, pos, ei, attr, y, device):
         self.device = torch.device(device)
         self.nodes, self.edges = nodes, edges

@@ -155,11 +155,16 @@ class AOMatrices:
             return cls(*(torch.from_numpy(z[k]) if k in z.files else None for k in _FLAT))
 
 
-def ao_edge_features(ao: AOMatrices, edge_index: torch.Tensor, atom_mol: torch.Tensor) -> torch.Tensor:
+def ao_edge_features(ao: AOMatrices, edge_index: torch.Tensor, atom_mol: torch.Tensor,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
     """``edge_attr`` float32 [E, 338] on the device, one launch (x2g_ao_edge_features).  ``edge_index`` int64
     [2, E] holds indices into ``atom_mol`` / ``ao.ao_begin`` (batch-global, edges in any order); ``atom_mol`` [N] is
     the molecule of each atom (``ao.atom_mol()`` when the batch is every molecule of ``ao`` in order).  An edge the
-    kernel finds invalid (see the header) gets a NaN row.  CPU tensors raise: there is no CPU implementation."""
+    kernel finds invalid (see the header) gets a NaN row.  CPU tensors raise: there is no CPU implementation.
+
+    ``out``: a contiguous float32 [E, 338] tensor on the matrices' device, e.g. a row slice of a dataset's
+    ``edge_attr``; the rows are written there and ``out`` is returned (ValueError for another shape, dtype, device
+    or layout).  Without it a new tensor is returned."""
     for name, t in (("ao", ao.ovlp), ("edge_index", edge_index), ("atom_mol", atom_mol)):
         if not t.is_cuda:
             raise RuntimeError(f"ao_edge_features needs GPU tensors, {name} is on {t.device} (no CPU fallback by "
@@ -169,7 +174,12 @@ def ao_edge_features(ao: AOMatrices, edge_index: torch.Tensor, atom_mol: torch.T
     if atom_mol.dim() != 1 or atom_mol.shape[0] != ao.num_atoms:
         raise ValueError(f"atom_mol has shape {tuple(atom_mol.shape)} for {ao.num_atoms} atoms")
     E = int(edge_index.shape[1])
-    out = torch.empty((E, EDGE_FEATURES), device=ao.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((E, EDGE_FEATURES), device=ao.device, dtype=torch.float32)
+    elif (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (E, EDGE_FEATURES)
+          or out.device != ao.device or not out.is_contiguous()):
+        what = f"{out.dtype} {tuple(out.shape)} on {out.device}" if torch.is_tensor(out) else type(out).__name__
+        raise ValueError(f"out must be a contiguous float32 [{E}, {EDGE_FEATURES}] tensor on {ao.device}, got {what}")
     if E == 0:
         return out
     ei = edge_index.to(torch.int64).contiguous()
