@@ -11,6 +11,7 @@ from .features import AOMatrices, ao_edge_features, bi_gen_edge_feature_6
 from .fit import fit
 from .graph import radius_graph
 from .init import reference_init_
+from .integrals import Basis, geom_scf_6, one_electron_matrices
 from .layers import AtomWise, EmbeddingBlock, F_B_2D, MolWise, RadialBasis, ResidualLayer, poly_envelop
 from .model import LayerNorm, SBFTransformer, SBFTransformerGlobal, SBFTransformerMulti, SBFTransformerV2
 from .plan import GraphPlan
@@ -20,9 +21,10 @@ from .train import Evaluator, Inference, Trainer
 from .xgnn import xgnn_poly, xgnn_poly_global, xgnn_poly_multi, xgnn_poly_v2
 
 __all__ = [
-    "AOMatrices", "AtomWise", "Batch", "Data", "DeviceDataset", "EmbeddingBlock", "Evaluator", "F_B_2D", "GraphPlan",
-    "Inference", "LayerNorm", "MolWise", "Plateau", "RadialBasis", "ResidualLayer", "SBFTransformer",
+    "AOMatrices", "AtomWise", "Basis", "Batch", "Data", "DeviceDataset", "EmbeddingBlock", "Evaluator", "F_B_2D",
+    "GraphPlan", "Inference", "LayerNorm", "MolWise", "Plateau", "RadialBasis", "ResidualLayer", "SBFTransformer",
     "SBFTransformerConv", "SBFTransformerGlobal", "SBFTransformerMulti", "SBFTransformerV2", "Trainer",
-    "ao_edge_features", "bi_gen_edge_feature_6", "collate", "fit", "molecule_to_data", "poly_envelop",
-    "radius_graph", "reference_init_", "xgnn_poly", "xgnn_poly_global", "xgnn_poly_multi", "xgnn_poly_v2",
+    "ao_edge_features", "bi_gen_edge_feature_6", "collate", "fit", "geom_scf_6", "molecule_to_data",
+    "one_electron_matrices", "poly_envelop", "radius_graph", "reference_init_", "xgnn_poly", "xgnn_poly_global",
+    "xgnn_poly_multi", "xgnn_poly_v2",
 ]

@@ -35,6 +35,8 @@ TRAIN_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_train.h")
 FEATURES_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_features.h")
 # the radius graph's header (x2gnn.graph: bonds and per-molecule counts from positions): a table of its own too
 GRAPH_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_graph.h")
+# the one-electron integrals' header (x2gnn.integrals: S and H_core from geometry and a basis set): one more table
+INTEGRALS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "x2g_integrals.h")
 
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int": ctypes.c_int,
             "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
@@ -151,6 +153,8 @@ TRAIN_SIGNATURES, TRAIN_RESTYPES = _read_functions(TRAIN_HEADER_PATH)
 FEATURES_SIGNATURES, FEATURES_RESTYPES = _read_functions(FEATURES_HEADER_PATH)
 # and for the radius graph (x2g_graph.h)
 GRAPH_SIGNATURES, GRAPH_RESTYPES = _read_functions(GRAPH_HEADER_PATH)
+# and for the one-electron integrals (x2g_integrals.h)
+INTEGRALS_SIGNATURES, INTEGRALS_RESTYPES = _read_functions(INTEGRALS_HEADER_PATH)
 
 _lib = None
 
@@ -169,7 +173,7 @@ def load():
         for sigs, res in ((STAGED_SIGNATURES, STAGED_RESTYPES), (MULTI_SIGNATURES, MULTI_RESTYPES),
                           (CONV_SIGNATURES, CONV_RESTYPES), (ATOMCTX_SIGNATURES, ATOMCTX_RESTYPES),
                           (TRAIN_SIGNATURES, TRAIN_RESTYPES), (FEATURES_SIGNATURES, FEATURES_RESTYPES),
-                          (GRAPH_SIGNATURES, GRAPH_RESTYPES)):
+                          (GRAPH_SIGNATURES, GRAPH_RESTYPES), (INTEGRALS_SIGNATURES, INTEGRALS_RESTYPES)):
             for name, args in sigs.items():
                 # (a library built from an earlier tree, X2G_LIB, has none of them: calling one then raises)
                 fn = getattr(lib, name, None)

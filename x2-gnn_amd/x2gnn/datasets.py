@@ -18,7 +18,8 @@
 * ``records_to_data`` — the whole ``mapping`` for a list of records whose overlap and
   core-Hamiltonian matrices are at hand (:class:`x2gnn.features.AOMatrices`, from pyscf elsewhere
   or from a file): the same bonds, and the real ``edge_attr`` of scf.py:50-119 computed on the
-  device, many molecules per launch.  Only the integrals themselves (``geom_scf_6``) need pyscf.
+  device, many molecules per launch.  With a :class:`x2gnn.integrals.Basis` in place of the matrices the integrals
+  (``geom_scf_6``) are computed on the device too, and nothing of the pipeline needs pyscf.
   (``DeviceDataset.from_records`` builds the same dataset with the bonds made on the device too,
   :mod:`x2gnn.graph`, and no feature row on the host.)
 * ``load_collated`` — a PyG ``InMemoryDataset`` processed file (qm9_allprop.py:58,
@@ -195,17 +196,24 @@ def record_to_data(rec: MolRecord, edge_attr: torch.Tensor | None = None, cutoff
 
 def records_to_data(records, ao, device, cutoff: float = 5.0, max_edges_per_launch: int = 1 << 18) -> list:
     """qm9_allprop.py:11-19 ``mapping`` for every record, with the features made on ``device`` from ``ao``
-    (:class:`x2gnn.features.AOMatrices`, molecule k belonging to ``records[k]``).  Bonds are
+    (:class:`x2gnn.features.AOMatrices`, molecule k belonging to ``records[k]``, or a
+    :class:`x2gnn.integrals.Basis`: the matrices' blocks of each launch's bonds are then computed on the device from
+    the positions in ``rec.atom``, parsed in float64).  Bonds are
     :func:`record_to_data`'s; the reference's check ``aoslice.shape[0] == edge_index.max() + 1``
     (qm9_allprop.py:15) raises ValueError naming the record.  As many whole molecules as fit
     ``max_edges_per_launch`` edges share one launch (a molecule with more edges than that gets one of its own);
     only their matrices are on the device at a time.  Each ``Data`` carries its CPU float32 ``edge_attr`` slice."""
     from .features import ao_edge_features
+    from .integrals import Basis, one_electron_matrices, record_geometries
 
     records = list(records)
-    if len(ao) != len(records):
-        raise ValueError(f"{len(ao)} molecules of AO matrices for {len(records)} records")
-    atom_start = ao.atom_start.numpy()
+    basis = ao if isinstance(ao, Basis) else None
+    if basis is None:
+        if len(ao) != len(records):
+            raise ValueError(f"{len(ao)} molecules of AO matrices for {len(records)} records")
+        atom_start = ao.atom_start.numpy()
+    else:
+        pos64, atom_start = record_geometries(records)
     eis = []
     for k, rec in enumerate(records):
         ei = bonds(distance_matrix(rec.R), cutoff)
@@ -221,10 +229,16 @@ def records_to_data(records, ao, device, cutoff: float = 5.0, max_edges_per_laun
         while hi < len(records) and total + eis[hi].shape[1] <= max_edges_per_launch:
             total += eis[hi].shape[1]
             hi += 1
-        part = ao.slice(lo, hi).to(device)
         offs = atom_start[lo:hi] - atom_start[lo]
-        ei_all = torch.cat([ei + int(o) for ei, o in zip(eis[lo:hi], offs)], dim=1)
-        attr = ao_edge_features(part, ei_all.to(device), part.atom_mol()).cpu()
+        ei_all = torch.cat([ei + int(o) for ei, o in zip(eis[lo:hi], offs)], dim=1).to(device)
+        if basis is None:
+            part = ao.slice(lo, hi).to(device)
+        else:
+            a0, a1 = int(atom_start[lo]), int(atom_start[hi])
+            Z = np.concatenate([np.asarray(r.Z, dtype=np.int64).reshape(-1) for r in records[lo:hi]])
+            part = one_electron_matrices(torch.from_numpy(pos64[a0:a1]).to(device), Z, atom_start[lo:hi + 1] - a0,
+                                         basis, pairs=ei_all)
+        attr = ao_edge_features(part, ei_all, part.atom_mol()).cpu()
         at = 0
         for k in range(lo, hi):
             E = eis[k].shape[1]

@@ -121,16 +121,21 @@ class DeviceDataset:
         feature row ever on the host.
 
         ``records``: :class:`x2gnn.datasets.MolRecord`; ``ao``: :class:`x2gnn.features.AOMatrices`, molecule k
-        belonging to ``records[k]``.  The reference's check ``aoslice.shape[0] == edge_index.max() + 1``
+        belonging to ``records[k]``, or a :class:`x2gnn.integrals.Basis`: each chunk's matrices are then computed on
+        the device (:func:`x2gnn.integrals.one_electron_matrices`, only the atom-pair blocks of that chunk's bonds)
+        from positions parsed from ``rec.atom`` in float64, as ``geom_scf_6`` takes them, so that nothing but
+        positions, ``Z`` and labels is uploaded.  The reference's check ``aoslice.shape[0] == edge_index.max() + 1``
         (qm9_allprop.py:15; the atom count for a molecule without an edge) raises ValueError naming the record
         before any feature launch, a molecule count that differs raises ValueError, and a device that is no GPU
         raises RuntimeError: there is no CPU implementation."""
         from .features import ao_edge_features
         from .graph import radius_graph
+        from .integrals import Basis, one_electron_matrices, record_geometries
         from .synth import EDGE_FEATURES
 
         records = list(records)
-        if len(ao) != len(records):
+        basis = ao if isinstance(ao, Basis) else None
+        if basis is None and len(ao) != len(records):
             raise ValueError(f"{len(ao)} molecules of AO matrices for {len(records)} records")
         device = torch.device(device)
         if device.type != "cuda":
@@ -159,7 +164,11 @@ class DeviceDataset:
 
         self.x, self.atom_pos, self.y = up(x), up(pos), up(y)
         g = radius_graph(self.atom_pos, self.atom_start, cutoff)
-        ao_start = ao.atom_start.numpy().astype(np.int64)
+        if basis is None:
+            ao_start = ao.atom_start.numpy().astype(np.int64)
+        else:
+            pos64, ao_start = record_geometries(records)
+            pos64 = up(pos64)
         top = np.where(g.last_bonded >= 0, g.last_bonded.astype(np.int64) + 1, nodes)
         bad = np.flatnonzero(np.diff(ao_start) != top)
         if bad.size:
@@ -181,11 +190,16 @@ class DeviceDataset:
                 hi += 1
             if total:
                 e0, e1 = int(self.edge_start[lo]), int(self.edge_start[hi])
-                part = ao.slice(lo, hi).to(device)
                 # local ids -> the chunk's atom numbering, which is the matrices' (ao.atom_start), not the records'
                 shift = torch.repeat_interleave(up(ao_start[lo:hi] - ao_start[lo]), up(self.edges[lo:hi]),
                                                 output_size=total)
-                ao_edge_features(part, self.edge_index[:, e0:e1] + shift, part.atom_mol(), out=self.edge_attr[e0:e1])
+                bonds = self.edge_index[:, e0:e1] + shift
+                if basis is None:
+                    part = ao.slice(lo, hi).to(device)
+                else:
+                    a0, a1 = int(ao_start[lo]), int(ao_start[hi])
+                    part = one_electron_matrices(pos64[a0:a1], x[a0:a1], ao_start[lo:hi + 1] - a0, basis, pairs=bonds)
+                ao_edge_features(part, bonds, part.atom_mol(), out=self.edge_attr[e0:e1])
             lo = hi
         self.mol_trips = up(self.triplets)
         self._stage, self._slot, self._debug_fill = None, 0, None

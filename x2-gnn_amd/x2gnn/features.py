@@ -2,8 +2,8 @@
 from overlap and core-Hamiltonian matrices, as one kernel (csrc/ao_features.hip, include/x2g_features.h).
 
 The reference makes the matrices with pyscf (``geom_scf_6``) and then turns them into features with a Python loop
-over edges.  Only the first half needs pyscf.  This module is the second half: whoever has S and H_core from any
-integral code, pyscf elsewhere or a file of matrices, gets the real ``edge_attr`` on the device.
+over edges.  This module is the second half: whoever has S and H_core from any integral code, pyscf elsewhere, a file
+of matrices or :mod:`x2gnn.integrals` (the first half, on the device too), gets the real ``edge_attr`` on the device.
 
 * :class:`AOMatrices` is the flat container the ABI takes: the matrices of M molecules end to end, each atom's AO
   range, and optionally the divisor of each molecule's H_core (the reference divides it by the electron count).
